@@ -5,6 +5,7 @@ clock — on synthetic text of the named shape (49,158,635 words, 197 splits
 per GPU; weak scaling: each rank owns one Europarl-size corpus).
 
   python bench.py --gpus 1 --steps 20 --warmup 5
+  python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
       --master-addr 127.0.0.1 bench.py --gpus 8 ...
 
@@ -17,6 +18,12 @@ job still executes completely and exactly one job's work falls in each
 timed step (steady state); MR_PIPELINE=0 forces sequential steps.
 Reference headline to beat: 49.23 s / ~1.0 M words/s on 4 CPU workers
 (BASELINE.md).
+
+A plain run does only what the headline figure needs: set up, warm up,
+time --steps steps, optionally --dump-outputs, print one JSON line.
+Secondary measurements belong behind --full (off by default); today the
+benchmark has none that run unasked (--from-disk and --timing are
+explicit options), so --full adds nothing to a plain run.
 """
 
 from __future__ import annotations
@@ -29,6 +36,53 @@ import time
 import torch
 
 BASELINE_WORDS_PER_SEC = 49_158_635 / 49.23  # BASELINE.md README.md:73
+
+# --dump-outputs: total size ceiling, shared evenly by the arrays written
+DUMP_BUDGET_BYTES = 60 << 20
+DUMP_SAMPLE_SEED = 20240229
+
+
+def _capped(arr, max_bytes):
+    """`arr` itself when it fits in max_bytes, else a fixed seeded sample
+    of its elements (same indices every run for the same length)."""
+    import numpy as np
+
+    k = max_bytes // arr.itemsize
+    if arr.size <= k:
+        return arr
+    rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+    idx = np.unique(rng.integers(0, arr.size, size=k))
+    return arr[idx]
+
+
+def dump_outputs(res, out_dir, rank=0, world=1):
+    """Write what the timed path's last step delivered — the arrays
+    WordCountResult.materialize() hands a caller (hash-ordered keys,
+    counts, exemplar word lengths, packed exemplar bytes) plus the job's
+    word total — as <name>.npy (rank 0 / single rank) or
+    <name>_rank<r>.npy.  u64 hash keys are split into exact 32-bit halves
+    (keys_hi, keys_lo) because float64 holds 53 bits; counts/lens are
+    exact in float64; word bytes go out as float32."""
+    import os
+
+    import numpy as np
+
+    keys, counts, lens, blob = res.materialize(blocking=True)
+    ku = keys.numpy().view(np.uint64)
+    arrays = {
+        "keys_hi": (ku >> np.uint64(32)).astype(np.float64),
+        "keys_lo": (ku & np.uint64(0xFFFFFFFF)).astype(np.float64),
+        "counts": counts.numpy().astype(np.float64),
+        "word_lens": lens.numpy().astype(np.float64),
+        "word_bytes": blob.numpy().astype(np.float32),
+        "nwords": np.array([res.nwords], dtype=np.float64),
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "" if world == 1 else f"_rank{rank}"
+    per = DUMP_BUDGET_BYTES // len(arrays)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"),
+                _capped(np.ascontiguousarray(a), per))
 
 
 def _self_launch(n: int) -> int:
@@ -75,6 +129,12 @@ def main() -> int:
                    help="bypass the control plane (engine-only timing)")
     p.add_argument("--timing", action="store_true",
                    help="print per-phase HIP-event times to stderr")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last timed "
+                        "step's delivered results as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run the secondary measurements (none today: "
+                        "a plain run already measures only the headline)")
     args = p.parse_args()
 
     import os
@@ -262,6 +322,8 @@ def main() -> int:
     total_words_per_step = args.words * world
     assert res is not None and res.nwords == args.words, \
         f"word count mismatch: {res.nwords} != {args.words}"
+    if args.dump_outputs:
+        dump_outputs(res, args.dump_outputs, rank=rank, world=world)
     resident_value = total_words_per_step * args.steps / elapsed
     if streamed_elapsed is not None:
         # the headline becomes the ingestion-inclusive number; the

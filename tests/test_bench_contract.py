@@ -68,6 +68,52 @@ def test_bench_single_process_contract():
     assert d["config"]["parallelism"] == "dp1"
 
 
+def test_bench_dump_outputs_and_full(tmp_path):
+    """--dump-outputs writes the last timed step's delivered results as
+    float .npy files, identical from run to run (same arguments -> same
+    inputs), and they are the word count of the corpus; --full is
+    accepted and keeps the headline line intact."""
+    import numpy as np
+
+    args = ["bench.py", "--steps", "2", "--warmup", "1",
+            "--words", "20000", "--splits", "4", "--vocab", "500",
+            "--device", "cpu"]
+    dumps = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        out = tmp_path / name
+        d = run_bench(args + ["--dump-outputs", str(out)] + extra)
+        assert d["metric"] == "words/sec" and d["ms_per_step"] > 0
+        assert d["steps"] == 2
+        dumps.append({f[:-4]: np.load(out / f)
+                      for f in sorted(os.listdir(out))})
+    a, b = dumps
+    assert set(a) == {"keys_hi", "keys_lo", "counts", "word_lens",
+                      "word_bytes", "nwords"}
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64)
+        assert np.array_equal(a[k], b[k]), k
+    assert a["nwords"].tolist() == [20000.0]
+    assert a["counts"].sum() == 20000
+    n = a["counts"].size
+    assert 0 < n <= 500
+    assert a["keys_hi"].size == a["keys_lo"].size == a["word_lens"].size == n
+    assert a["word_bytes"].size == a["word_lens"].sum()
+    # the dumped words are the corpus' words with their true counts
+    sys.path.insert(0, REPO)
+    import collections
+
+    from mapreduce_amd.gpu.corpus import make_corpus
+    corpus = make_corpus("cpu", nwords=20000, nsplits=4, vocab_size=500,
+                         seed=1234)
+    exp = collections.Counter(corpus.text.numpy().tobytes().split())
+    raw = a["word_bytes"].astype(np.uint8).tobytes()
+    got, off = {}, 0
+    for L, c in zip(a["word_lens"].astype(int), a["counts"].astype(int)):
+        got[raw[off:off + L]] = int(c)
+        off += L
+    assert got == dict(exp)
+
+
 @pytest.mark.timeout(500)
 def test_bench_torchrun_ws4_contract():
     """4-rank canary for the driver's N=4/8 scaling runs."""
