@@ -5,6 +5,10 @@ distinct keys to the global table; more slices = better load balance but
 ~slices-fold redundant global flushes per bucket.  The original sweep
 (8=3.19, 16=2.58, 32=2.38 ms/step) ran when chunk-tail pads skewed bucket
 255 by ~2M entries; the 2048-entry allocator changed that.
+
+Each argument is SLICES or SLICESxSLOTS (e.g. 32 or 32x2048): the second
+field sets MR_BKT_SLOTS, the bucket_count LDS table size, for a joint
+sweep; without it the caller's default table size is used.
 """
 
 import os
@@ -27,7 +31,12 @@ def main():
     splits = corpus.splits()
     steps, warm = 15, 5
     for setting in sys.argv[1:] or ["32", "16", "8", "64", "32"]:
-        os.environ["MR_BUCKET_SLICES"] = setting
+        slices, _, slots = setting.partition("x")
+        os.environ["MR_BUCKET_SLICES"] = slices
+        if slots:
+            os.environ["MR_BKT_SLOTS"] = slots
+        else:
+            os.environ.pop("MR_BKT_SLOTS", None)
         for _ in range(warm):
             job.run(corpus.text, splits)
         torch.cuda.synchronize()

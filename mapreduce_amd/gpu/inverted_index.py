@@ -190,8 +190,8 @@ class InvertedIndexJob:
             # stream measured ~20 ms of a 26 ms job).  doc is recoverable
             # from the exemplar position, so wordhash = k2 ^
             # splitmix64(doc) reverses the composite.  HT_EMPTY chunk
-            # padding flows through — the radix pass groups it in bucket
-            # 255 and bucket_count skips it.
+            # padding stops at the bucketize (radix_bucketize skip mode;
+            # 8.06 vs 8.52 ms/job with the pads carried through).
             # MR_II_CACHE=1: LDS-cached composite tokenizer — MEASURED
             # SLOWER (9.16 vs 9.00 ms): the grid-stride tile mapping
             # spreads each block over ~30 tiles of DIFFERENT documents,
@@ -226,10 +226,8 @@ class InvertedIndexJob:
                         f"spill overflow: {n} reserved > {cap}")
                 k2, p = k2[:n], p[:n]
             if n:
-                hk, pv, totals = ops.ext().radix_pass(k2, p, 56)
-                bucket_off = torch.zeros(257, dtype=torch.int64,
-                                         device=dev)
-                torch.cumsum(totals, 0, out=bucket_off[1:])
+                hk, pv, bucket_off = ops.ext().radix_bucketize(
+                    k2, p, 56, True)
                 # r2 joint re-sweep on the idx32 tree (the knobs
                 # INTERACT): 1024 slots x 128 slices = 8.48 ms vs the
                 # old 2048x64 = 8.91 (-4.8%).  Full grid: slices at

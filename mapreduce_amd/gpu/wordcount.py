@@ -6,7 +6,8 @@ Per step (= one full MapReduce job over the rank's corpus):
                 LDS cache tables count the Zipf head in-kernel (the
                 reference's mapfn emit + inline combiner job.lua:83-97);
                 cache misses spill through the wave-chunked allocator,
-                then one radix_pass(56) bucketize + per-bucket LDS count
+                then one top-byte bucketize (radix_bucketize, which also
+                drops the allocator's pads) + per-bucket LDS count
                 (bucket_count) drains them — every per-word atomic is an
                 LDS atomic.
   EXTRACT+SORT  table -> unique (hash, count, exemplar pos); sort by hash
@@ -33,6 +34,10 @@ import torch
 
 from .. import ops
 from . import dist as dx
+
+
+# bucket_count slices per top-byte bucket (MR_BUCKET_SLICES overrides)
+DEFAULT_BUCKET_SLICES = 16
 
 
 @dataclass
@@ -322,7 +327,8 @@ class WordCountJob:
     def _finish_map_inner(self) -> int:
         if self.mode == "streaming":
             import os
-            slices = int(os.environ.get("MR_BUCKET_SLICES", "64"))
+            slices = int(os.environ.get("MR_BUCKET_SLICES",
+                                        DEFAULT_BUCKET_SLICES))
             if self._bspill:
                 # misses are already bucket-partitioned in per-bucket
                 # regions; counters hold exact per-bucket lengths
@@ -354,18 +360,23 @@ class WordCountJob:
             if nspill:
                 h = self._spill_h[:nspill]
                 p = self._spill_p[:nspill]
-                hk, pv, totals = ops.ext().radix_pass(h, p, 56)
-                bucket_off = torch.zeros(257, dtype=torch.int64,
-                                         device=self.device)
-                torch.cumsum(totals, 0, out=bucket_off[1:])
-                # 64 slices/bucket (re-swept at 1024-slot tables:
-                # 16=1.73, 32=1.60, 48=1.55, 64=1.53, 96=1.56 ms/step —
-                # smaller slices raise block-level parallelism and keep
-                # bucket-255's pad skew off the critical path)
-                # 1024 LDS slots: ~390 distinct/slice fits 2.6x over;
-                # 20 KB = 8 blocks/CU (sweep: 2048=1.71, 1024=1.60,
-                # 512=1.64 ms/step — the kernel is occupancy/latency
-                # bound, profiles/pmc_final_kernels.txt)
+                # the bucketize drops the allocator's HT_EMPTY chunk-tail
+                # pads (~2.85M of 16.8M reserved slots on the bench
+                # shape; they would all land in bucket 255) and returns
+                # bucket_off from its native scan; hk/pv keep length
+                # nspill, defined up to bucket_off[256]
+                hk, pv, bucket_off = ops.ext().radix_bucketize(
+                    h, p, 56, True)
+                # 16 slices/bucket x 1024 LDS slots, re-swept without
+                # the pad tail (profiles/drain_skip_r03.md): 8=1.349,
+                # 16=1.307, 24=1.333, 32=1.334, 48=1.365, 64=1.388
+                # ms/step; 2048 slots: 8=1.335, rising to 64=1.512.  The
+                # old 64-slice optimum only kept bucket-255's pads off
+                # the critical path; fewer slices cut the scattered
+                # global flush atomics 3.97M -> 1.75M per job.  1024
+                # slots = 20 KB = 8 blocks/CU (the kernel is occupancy/
+                # latency bound, profiles/pmc_final_kernels.txt);
+                # overflow degrades to per-element ht_add, never wrong.
                 ops.ext().bucket_count(hk, pv, bucket_off, 256, slices,
                                        self.table.tkeys, self.table.tvals,
                                        self.table.texm, 0, 1024)

@@ -46,6 +46,11 @@ int rs_items() {
 
 long rs_tile() { return (long)RS_BLOCK * rs_items(); }
 
+bool radix_v1_forced() {
+  const char* v = getenv("MR_RADIX_V1");
+  return v && v[0] == '1';
+}
+
 void launch_radix_hist(const u64* kin, long n, int shift, long ntiles,
                        i64* hist) {
   auto kfn = rs_items() == 4 ? radix_hist_kernel<4> : radix_hist_kernel<8>;
@@ -57,10 +62,7 @@ void launch_radix_scatter(const u64* kin, const u64* vin, long n, int shift,
                           long ntiles, const i64* base, u64* kout,
                           u64* vout) {
   static int use_v1 = -1;
-  if (use_v1 < 0) {
-    const char* v = getenv("MR_RADIX_V1");
-    use_v1 = (v && v[0] == '1') ? 1 : 0;
-  }
+  if (use_v1 < 0) use_v1 = radix_v1_forced() ? 1 : 0;
   if (use_v1)
     hipLaunchKernelGGL(radix_scatter_kernel, dim3(ntiles), dim3(RS_BLOCK), 0,
                        cur_stream(), kin, vin, n, shift, ntiles, base, kout,
@@ -79,6 +81,28 @@ void launch_radix_scatter32(const u64* kin, const u32* vin, long n,
                             u64* kout, u32* vout) {
   auto kfn = rs_items() == 4 ? radix_scatter_v2_kernel<4, u32>
                              : radix_scatter_v2_kernel<8, u32>;
+  hipLaunchKernelGGL(kfn, dim3(ntiles), dim3(RS_BLOCK), 0, cur_stream(),
+                     kin, vin, n, shift, ntiles, base, kout, vout);
+}
+
+// bucketize launches: u32 histogram/base, optional HT_EMPTY skip (the
+// skip and payload type are template parameters, so the full-sort
+// instantiations above are untouched)
+template <bool SKIP>
+void launch_bucketize_hist(const u64* kin, long n, int shift, long ntiles,
+                           u32* hist) {
+  auto kfn = rs_items() == 4 ? radix_hist_kernel<4, SKIP, u32>
+                             : radix_hist_kernel<8, SKIP, u32>;
+  hipLaunchKernelGGL(kfn, dim3(ntiles), dim3(RS_BLOCK), 0, cur_stream(),
+                     kin, n, shift, ntiles, hist);
+}
+
+template <typename VT, bool SKIP>
+void launch_bucketize_scatter(const u64* kin, const VT* vin, long n,
+                              int shift, long ntiles, const u32* base,
+                              u64* kout, VT* vout) {
+  auto kfn = rs_items() == 4 ? radix_scatter_v2_kernel<4, VT, SKIP, u32>
+                             : radix_scatter_v2_kernel<8, VT, SKIP, u32>;
   hipLaunchKernelGGL(kfn, dim3(ntiles), dim3(RS_BLOCK), 0, cur_stream(),
                      kin, vin, n, shift, ntiles, base, kout, vout);
 }
@@ -805,6 +829,72 @@ std::vector<torch::Tensor> radix_pass(torch::Tensor keys, torch::Tensor vals,
   return {kout, vout, totals};
 }
 
+// The spill drain's bucketize: one partition pass on an 8-bit digit with
+// the scan done natively (u32 histogram -> rs_row_totals + rs_row_scan,
+// no ATen glue, no zero fill).  vals: int64 or int32 payload, or empty.
+// Returns (keys_out, vals_out, bucket_off[257]); outputs keep length n and
+// the first bucket_off[256] entries are defined.  skip_empty (default
+// off; spill drains only) drops HT_EMPTY-keyed records, so bucket_off
+// counts survivors; off, all-ones keys are ordinary data.  No host sync.
+// The direct-scatter A/B kernel (MR_RADIX_V1=1) has no skip predicate
+// and no u32 base, so this entry point refuses to run with it.
+std::vector<torch::Tensor> radix_bucketize(torch::Tensor keys,
+                                           torch::Tensor vals, long shift,
+                                           bool skip_empty) {
+  check_dev_i64(keys, "keys");
+  long n = keys.numel();
+  bool has_vals = vals.numel() > 0;
+  bool v32 = has_vals && vals.scalar_type() == torch::kInt32;
+  if (has_vals) {
+    TORCH_CHECK(vals.is_cuda() && vals.is_contiguous() && vals.numel() == n,
+                "vals must be contiguous on GPU, one per key");
+    TORCH_CHECK(v32 || vals.scalar_type() == torch::kInt64,
+                "vals must be int64 or int32");
+  }
+  TORCH_CHECK(shift >= 0 && shift <= 56, "shift in [0,56]");
+  TORCH_CHECK(n < (1L << 32), "bucketize positions are u32: n < 2^32");
+  TORCH_CHECK(!radix_v1_forced(),
+              "radix_bucketize has no direct-scatter (MR_RADIX_V1=1) form");
+  auto opts = keys.options();
+  auto kout = torch::empty({n}, opts);
+  auto vout = has_vals ? torch::empty({n}, vals.options())
+                       : torch::empty({0}, opts);
+  if (n == 0) return {kout, vout, torch::zeros({RS_BINS + 1}, opts)};
+  long ntiles = (n + rs_tile() - 1) / rs_tile();
+  auto bucket_off = torch::empty({RS_BINS + 1}, opts);
+  auto totals = torch::empty({RS_BINS}, opts);
+  auto hist = torch::empty({(long)RS_BINS * ntiles}, opts.dtype(torch::kInt32));
+  u32* hp = reinterpret_cast<u32*>(hist.data_ptr<int>());
+  int sh = (int)shift;
+  if (skip_empty) launch_bucketize_hist<true>(u64cp(keys), n, sh, ntiles, hp);
+  else launch_bucketize_hist<false>(u64cp(keys), n, sh, ntiles, hp);
+  hipLaunchKernelGGL(rs_row_totals_kernel, dim3(RS_BINS), dim3(RS_BLOCK), 0,
+                     cur_stream(), hp, ntiles, totals.data_ptr<i64>());
+  hipLaunchKernelGGL(rs_row_scan_kernel, dim3(RS_BINS), dim3(RS_BLOCK), 0,
+                     cur_stream(), hp, ntiles, totals.data_ptr<i64>(),
+                     bucket_off.data_ptr<i64>());
+  if (v32) {
+    const u32* vi = reinterpret_cast<const u32*>(vals.data_ptr<int>());
+    u32* vo = reinterpret_cast<u32*>(vout.data_ptr<int>());
+    if (skip_empty)
+      launch_bucketize_scatter<u32, true>(u64cp(keys), vi, n, sh, ntiles, hp,
+                                          u64p(kout), vo);
+    else
+      launch_bucketize_scatter<u32, false>(u64cp(keys), vi, n, sh, ntiles,
+                                           hp, u64p(kout), vo);
+  } else {
+    const u64* vi = has_vals ? u64cp(vals) : nullptr;
+    u64* vo = has_vals ? u64p(vout) : nullptr;
+    if (skip_empty)
+      launch_bucketize_scatter<u64, true>(u64cp(keys), vi, n, sh, ntiles, hp,
+                                          u64p(kout), vo);
+    else
+      launch_bucketize_scatter<u64, false>(u64cp(keys), vi, n, sh, ntiles,
+                                           hp, u64p(kout), vo);
+  }
+  return {kout, vout, bucket_off};
+}
+
 std::vector<torch::Tensor> radix_sort_pairs(torch::Tensor keys,
                                             torch::Tensor vals, int bits) {
   check_dev_i64(keys, "keys");
@@ -947,5 +1037,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gather_bytes", &gather_bytes);
   m.def("radix_sort_pairs", &radix_sort_pairs);
   m.def("radix_pass", &radix_pass);
+  m.def("radix_bucketize", &radix_bucketize, py::arg("keys"),
+        py::arg("vals"), py::arg("shift"), py::arg("skip_empty") = false,
+        "one-digit partition with native scan -> (keys, vals, bucket_off)");
   m.def("grad_colsum", &grad_colsum, "sum G gradient rows -> D (K6)");
 }

@@ -10,6 +10,12 @@
 //      order makes the scan produce exactly base[d][t]
 //   3. radix_scatter_kernel  — stable scatter to base[d][t] + local rank
 //
+// SKIP mode (spill-drain bucketize only): records whose key is HT_EMPTY —
+// the spill allocator's chunk-tail pads — are neither counted nor written,
+// so they stop at the first kernel that reads them.  The predicate is
+// rs_live<SKIP>() in BOTH kernels; SKIP=false compiles to the plain pass
+// (real sort keys may legitimately be all-ones).
+//
 // Replaces the reference's table.sort + heap merge (job.lua:194,
 // utils.lua:206-271): sort once, then segment (K4 -> K1+K5).
 
@@ -25,10 +31,15 @@
 // v2 scatter, 4 blocks/CU); 4 -> 1024 (22 KB, 7 blocks/CU) — occupancy
 // vs digit-run length (write coalescing) tradeoff, selected per size by
 // MR_RS_ITEMS.
-template <int ITEMS>
+template <bool SKIP>
+DEV bool rs_live(u64 k) { return !SKIP || k != HT_EMPTY; }
+
+// HT: histogram entry type.  i64 feeds the torch cumsum of the full sort;
+// u32 (a tile holds <= 2048 records) feeds the native bucketize scan.
+template <int ITEMS, bool SKIP = false, typename HT = i64>
 __global__ __launch_bounds__(RS_BLOCK) void radix_hist_kernel(
     const u64* __restrict__ keys, long n, int shift, long ntiles,
-    i64* __restrict__ hist) {
+    HT* __restrict__ hist) {
   __shared__ u32 lh[RS_BINS];
   for (int b = threadIdx.x; b < RS_BINS; b += blockDim.x) lh[b] = 0;
   __syncthreads();
@@ -37,13 +48,13 @@ __global__ __launch_bounds__(RS_BLOCK) void radix_hist_kernel(
   for (int r = 0; r < ITEMS; ++r) {
     long i = base + r * RS_BLOCK + threadIdx.x;
     if (i < n) {
-      u32 d = (u32)((keys[i] >> shift) & 0xFF);
-      atomicAdd(&lh[d], 1u);
+      u64 k = keys[i];
+      if (rs_live<SKIP>(k)) atomicAdd(&lh[(u32)((k >> shift) & 0xFF)], 1u);
     }
   }
   __syncthreads();
   for (int b = threadIdx.x; b < RS_BINS; b += blockDim.x)
-    hist[(long)b * ntiles + tile] = (i64)lh[b];
+    hist[(long)b * ntiles + tile] = (HT)lh[b];
 }
 
 // v2: LDS-staged scatter.  v1 writes each element straight to its global
@@ -60,10 +71,13 @@ __global__ __launch_bounds__(RS_BLOCK) void radix_hist_kernel(
 // one extra resident block), for callers that gather their real payload
 // once through the final permutation instead of dragging it through
 // every pass (TeraSort, sort_by_key).
-template <int ITEMS, typename VT = u64>
+// SKIP: drop HT_EMPTY records (see header); the tile then stages only
+// digit_start[RS_BINS] <= tile_n records and streams out exactly those.
+// BT: base_dx entry type (i64 from the torch scan, u32 from the native one).
+template <int ITEMS, typename VT = u64, bool SKIP = false, typename BT = i64>
 __global__ __launch_bounds__(RS_BLOCK) void radix_scatter_v2_kernel(
     const u64* __restrict__ keys, const VT* __restrict__ vals, long n,
-    int shift, long ntiles, const i64* __restrict__ base_dx,
+    int shift, long ntiles, const BT* __restrict__ base_dx,
     u64* __restrict__ okeys, VT* __restrict__ ovals) {
   __shared__ u32 wavecnt[RS_WAVES][RS_BINS];
   __shared__ u32 cnt_base[RS_BINS];     // running per-digit counts
@@ -83,8 +97,11 @@ __global__ __launch_bounds__(RS_BLOCK) void radix_scatter_v2_kernel(
   __syncthreads();
   for (int r = 0; r < ITEMS; ++r) {
     long i = tbase + (long)r * RS_BLOCK + threadIdx.x;
-    if (i < n)
-      atomicAdd(&cnt_base[(u32)((keys[i] >> shift) & 0xFF)], 1u);
+    if (i < n) {
+      u64 k = keys[i];
+      if (rs_live<SKIP>(k))
+        atomicAdd(&cnt_base[(u32)((k >> shift) & 0xFF)], 1u);
+    }
   }
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -107,6 +124,7 @@ __global__ __launch_bounds__(RS_BLOCK) void radix_scatter_v2_kernel(
     long i = tbase + (long)r * RS_BLOCK + threadIdx.x;
     bool valid = i < n;
     u64 k = valid ? keys[i] : 0;
+    valid = valid && rs_live<SKIP>(k);
     u32 d = valid ? (u32)((k >> shift) & 0xFF) : 0;
     u64 m = __ballot(valid);
     #pragma unroll
@@ -140,12 +158,15 @@ __global__ __launch_bounds__(RS_BLOCK) void radix_scatter_v2_kernel(
     __syncthreads();
   }
 
-  // ---- stream out in stage order: coalesced within each digit run
-  for (long s = threadIdx.x; s < tile_n; s += blockDim.x) {
+  // ---- stream out in stage order: coalesced within each digit run.
+  // SKIP staged only the live records: slots past digit_start[RS_BINS]
+  // were never written and must not be read.
+  long nstage = SKIP ? (long)digit_start[RS_BINS] : tile_n;
+  for (long s = threadIdx.x; s < nstage; s += blockDim.x) {
     u64 k = stage_k[s];
     u32 d = (u32)((k >> shift) & 0xFF);
     u32 local = (u32)s - digit_start[d];
-    long pos = base_dx[(long)d * ntiles + tile] + local;
+    long pos = (long)base_dx[(long)d * ntiles + tile] + local;
     okeys[pos] = k;
     if (has_vals) ovals[pos] = stage_v[s];
   }
@@ -210,6 +231,111 @@ __global__ __launch_bounds__(RS_BLOCK) void radix_scatter_kernel(
       okeys[pos] = k;
       if (ovals) ovals[pos] = vals[i];
     }
+    __syncthreads();
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Native scan between the bucketize histogram and scatter (two launches,
+// RS_BINS blocks each) — replaces zeros + cumsum + subtract + row-sum +
+// zeros(257) + cumsum over a [256 x ntiles] i64 array with two passes over
+// a u32 one.
+//   1. rs_row_totals_kernel: totals[d] = sum_t hist[d][t]
+//   2. rs_row_scan_kernel:   bucket_off[d] = sum_{e<d} totals[e] (each block
+//      re-reduces the 256 totals), then hist[d][t] <- bucket_off[d] +
+//      exclusive row prefix, IN PLACE: the flat digit-major exclusive scan
+//      base[d][t] the scatter consumes.  Positions are u32 (host checks
+//      n < 2^32).
+// ---------------------------------------------------------------------------
+#define RS_SCAN_UNROLL 4
+
+DEV u32 wave_incl_scan_u32(u32 v, int lane) {
+  #pragma unroll
+  for (int off = 1; off < WAVE; off <<= 1) {
+    u32 o = __shfl_up(v, off, WAVE);
+    if (lane >= off) v += o;
+  }
+  return v;
+}
+
+__global__ __launch_bounds__(RS_BLOCK) void rs_row_totals_kernel(
+    const u32* __restrict__ hist, long ntiles, i64* __restrict__ totals) {
+  __shared__ i64 wsum[RS_WAVES];
+  const u32* row = hist + (long)blockIdx.x * ntiles;
+  i64 acc = 0;
+  for (long t0 = threadIdx.x; t0 < ntiles; t0 += RS_SCAN_UNROLL * RS_BLOCK) {
+    u32 v[RS_SCAN_UNROLL];
+    #pragma unroll
+    for (int j = 0; j < RS_SCAN_UNROLL; ++j) {
+      long t = t0 + (long)j * RS_BLOCK;
+      v[j] = t < ntiles ? row[t] : 0;
+    }
+    #pragma unroll
+    for (int j = 0; j < RS_SCAN_UNROLL; ++j) acc += v[j];
+  }
+  acc = wave_sum_i64(acc);
+  if (threadIdx.x % WAVE == 0) wsum[threadIdx.x / WAVE] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    i64 s = 0;
+    for (int w = 0; w < RS_WAVES; ++w) s += wsum[w];
+    totals[blockIdx.x] = s;
+  }
+}
+
+__global__ __launch_bounds__(RS_BLOCK) void rs_row_scan_kernel(
+    u32* __restrict__ hist, long ntiles, const i64* __restrict__ totals,
+    i64* __restrict__ bucket_off) {
+  __shared__ i64 wsum[RS_WAVES];
+  __shared__ u32 wpre[RS_SCAN_UNROLL * RS_WAVES];
+  __shared__ i64 row_base;
+  int d = blockIdx.x;
+  int wave = threadIdx.x / WAVE;
+  int lane = threadIdx.x % WAVE;
+  // exclusive offset of digit d (+ the grand total from the last block)
+  i64 tv = totals[threadIdx.x];  // RS_BLOCK == RS_BINS
+  i64 part = wave_sum_i64(threadIdx.x < d ? tv : 0);
+  if (lane == 0) wsum[wave] = part;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    i64 s = 0;
+    for (int w = 0; w < RS_WAVES; ++w) s += wsum[w];
+    row_base = s;
+    bucket_off[d] = s;
+    if (d == RS_BINS - 1) bucket_off[RS_BINS] = s + totals[d];
+  }
+  __syncthreads();
+  u32 carry = (u32)row_base;
+  u32* row = hist + (long)d * ntiles;
+  // RS_SCAN_UNROLL sub-chunks of RS_BLOCK entries per round: their loads
+  // are issued together and one barrier pair serves all of them (the row
+  // walk is latency-bound, not byte-bound)
+  for (long t0 = 0; t0 < ntiles; t0 += RS_SCAN_UNROLL * RS_BLOCK) {
+    u32 v[RS_SCAN_UNROLL], inc[RS_SCAN_UNROLL];
+    #pragma unroll
+    for (int j = 0; j < RS_SCAN_UNROLL; ++j) {
+      long t = t0 + (long)j * RS_BLOCK + threadIdx.x;
+      v[j] = t < ntiles ? row[t] : 0;
+    }
+    #pragma unroll
+    for (int j = 0; j < RS_SCAN_UNROLL; ++j) {
+      inc[j] = wave_incl_scan_u32(v[j], lane);
+      if (lane == WAVE - 1) wpre[j * RS_WAVES + wave] = inc[j];
+    }
+    __syncthreads();
+    u32 run = carry;
+    #pragma unroll
+    for (int j = 0; j < RS_SCAN_UNROLL; ++j) {
+      #pragma unroll
+      for (int w = 0; w < RS_WAVES; ++w) {
+        if (w == wave) {
+          long t = t0 + (long)j * RS_BLOCK + threadIdx.x;
+          if (t < ntiles) row[t] = run + inc[j] - v[j];
+        }
+        run += wpre[j * RS_WAVES + w];
+      }
+    }
+    carry = run;
     __syncthreads();
   }
 }
