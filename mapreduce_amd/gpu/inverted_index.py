@@ -56,15 +56,67 @@ class InvertedIndexResult:
                               tf[offs[i]:offs[i + 1]]))
         return out
 
+    def lex_perm(self) -> torch.Tensor:
+        """Device permutation putting the words in lexicographic byte
+        order (ops.lex_order over the exemplars), computed once and
+        cached.  Hash order stays the arrays' native order."""
+        perm = getattr(self, "_lex_perm", None)
+        if perm is None:
+            perm = ops.lex_order(self.blob_src, self.pos)
+            self._lex_perm = perm
+        return perm
+
+    def _rows(self, idx: torch.Tensor):
+        """[(word, postings)] for the word rows idx, in idx order; only
+        those rows' exemplars and postings cross to the host."""
+        if idx.numel() == 0:
+            return []
+        lens, blob = ops.extract_words(self.blob_src,
+                                       self.pos.index_select(0, idx))
+        raw = bytes(blob.cpu().numpy().tobytes())
+        o0 = self.doc_offsets.index_select(0, idx)
+        cnt = self.doc_offsets.index_select(0, idx + 1) - o0
+        # flat posting indices of the selected rows, row after row
+        ends = torch.cumsum(cnt, 0)
+        row = torch.repeat_interleave(
+            torch.arange(idx.numel(), device=idx.device), cnt)
+        flat = (torch.arange(row.numel(), device=idx.device)
+                - (ends - cnt).index_select(0, row)
+                + o0.index_select(0, row))
+        docs = self.docs.index_select(0, flat).cpu().tolist()
+        tf = self.tf.index_select(0, flat).cpu().tolist()
+        out = []
+        off = a = 0
+        for L, c in zip(lens.cpu().tolist(), cnt.cpu().tolist()):
+            out.append((raw[off:off + L],
+                        list(zip(docs[a:a + c], tf[a:a + c]))))
+            off += L
+            a += c
+        return out
+
     def pair_iterator(self, order: str = "hash"):
         """The reference finalfn contract (server.lua:360-385): yields
-        (word, postings-list) pairs; order="lex" sorts by word bytes at
-        the finalfn boundary (the reference's sorted-result guarantee)."""
-        items = self.to_host().items()
+        (word, postings-list) pairs; order="lex" walks the device
+        lexicographic permutation (the reference's sorted-result
+        guarantee) instead of sorting on the host."""
         if order == "lex":
-            items = sorted(items)
+            items = self._rows(self.lex_perm())
+        else:
+            items = self.to_host().items()
         for w, postings in items:
             yield w, postings
+
+    def prefix(self, p, limit: Optional[int] = None):
+        """[(word, postings)] for every word starting with p, in
+        lexicographic order (the first `limit` of them): the range
+        [lower_bound(p), lower_bound(succ(p))) of lex_perm()."""
+        if isinstance(p, str):
+            p = p.encode()
+        perm = self.lex_perm()
+        lo, hi = ops.lex_prefix_range(self.blob_src, self.pos, perm, p)
+        if limit is not None:
+            hi = min(hi, lo + max(0, int(limit)))
+        return self._rows(perm[lo:hi])
 
     def _signed_keys(self) -> torch.Tensor:
         """keys hold u64 bit patterns; XOR the sign bit maps unsigned

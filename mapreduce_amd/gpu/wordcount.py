@@ -102,11 +102,71 @@ class WordCountResult:
             return 0
         return int(self.counts[i].item())
 
-    def materialize(self, blocking: bool = True):
+    def lex_perm(self) -> torch.Tensor:
+        """Device permutation putting the words in lexicographic byte
+        order (ops.lex_order over the exemplars), computed once and
+        cached.  Hash order stays the arrays' native order."""
+        self._wait_ready()
+        perm = getattr(self, "_lex_perm", None)
+        if perm is None:
+            perm = ops.lex_order(self.blob_src, self.pos)
+            self._lex_perm = perm
+        return perm
+
+    def _ordered(self, order: str):
+        """(keys, counts, pos) in the requested order."""
+        if order != "lex":
+            return self.keys, self.counts, self.pos
+        perm = self.lex_perm()
+        return (self.keys.index_select(0, perm),
+                self.counts.index_select(0, perm),
+                self.pos.index_select(0, perm))
+
+    def _pairs(self, counts: torch.Tensor,
+               pos: torch.Tensor) -> List[Tuple[bytes, int]]:
+        lens, blob = ops.extract_words(self.blob_src, pos)
+        raw = bytes(blob.cpu().numpy().tobytes())
+        out = []
+        off = 0
+        for L, c in zip(lens.cpu().tolist(), counts.cpu().tolist()):
+            out.append((raw[off:off + L], c))
+            off += L
+        return out
+
+    def _prefix_range(self, p) -> Tuple[int, int]:
+        if isinstance(p, str):
+            p = p.encode()
+        return ops.lex_prefix_range(self.blob_src, self.pos,
+                                    self.lex_perm(), p)
+
+    def count_prefix(self, p) -> int:
+        """Number of distinct words starting with p: two device binary
+        searches on the lexicographic permutation, no exemplar traffic."""
+        lo, hi = self._prefix_range(p)
+        return hi - lo
+
+    def prefix(self, p, limit: Optional[int] = None
+               ) -> List[Tuple[bytes, int]]:
+        """All (word, count) with word starting with p, in lexicographic
+        order (the first `limit` of them) — the range
+        [lower_bound(p), lower_bound(succ(p))) of the permutation; only
+        the selected exemplars cross to the host, as in topk."""
+        lo, hi = self._prefix_range(p)
+        if limit is not None:
+            hi = min(hi, lo + max(0, int(limit)))
+        if hi <= lo:
+            return []
+        idx = self.lex_perm()[lo:hi]
+        return self._pairs(self.counts.index_select(0, idx),
+                           self.pos.index_select(0, idx))
+
+    def materialize(self, blocking: bool = True, order: str = "hash"):
         """Deliver the job's results to host memory (the analogue of the
         reference writing result.P<p> files + the server reading them,
         C7/C8): raw key/count arrays + the packed exemplar word bytes.
         One packed i64 D2H + one u8 D2H into cached pinned buffers.
+        order="lex" returns the same four arrays permuted into
+        lexicographic word order (lex_perm) on the device first.
 
         blocking=False enqueues the copies on the current stream and
         returns immediately — the next job's kernels overlap the D2H, and
@@ -114,9 +174,10 @@ class WordCountResult:
         complete (how bench.py uses it).  Returns (keys_cpu, counts_cpu,
         lens_cpu, blob_cpu)."""
         self._wait_ready()  # no-op for the producer's own in-stream call
-        lens, blob = ops.extract_words(self.blob_src, self.pos)
-        n = self.keys.numel()
-        packed = torch.cat([self.keys, self.counts, lens])
+        keys, counts, pos = self._ordered(order)
+        lens, blob = ops.extract_words(self.blob_src, pos)
+        n = keys.numel()
+        packed = torch.cat([keys, counts, lens])
         if packed.is_cuda:
             host = torch.empty(packed.shape, dtype=packed.dtype,
                                pin_memory=True)
@@ -136,21 +197,12 @@ class WordCountResult:
         order="hash" (default): the engine's native u64-hash order —
         deterministic and grouped, the order the device arrays are in.
         order="lex": lexicographic by word bytes, matching the reference's
-        sorted-result guarantee (job.lua:194, server.lua:360-385) — a
-        host-side sort of the (small) unique set at the finalfn boundary,
-        where the reference also pays its string costs."""
+        sorted-result guarantee (job.lua:194, server.lua:360-385) —
+        counts and exemplars are permuted on the device (lex_perm) before
+        extraction, so the host never sorts."""
         self._wait_ready()
-        lens, blob = ops.extract_words(self.blob_src, self.pos)
-        raw = bytes(blob.cpu().numpy().tobytes())
-        counts = self.counts.cpu().tolist()
-        out = []
-        off = 0
-        for L, c in zip(lens.cpu().tolist(), counts):
-            out.append((raw[off:off + L], c))
-            off += L
-        if order == "lex":
-            out.sort(key=lambda kv: kv[0])
-        return out
+        _, counts, pos = self._ordered(order)
+        return self._pairs(counts, pos)
 
     def pair_iterator(self, order: str = "hash"):
         """The reference finalfn contract (server.lua:360-385): yields
@@ -170,15 +222,7 @@ class WordCountResult:
         if k == 0:
             return []
         cnt, idx = torch.topk(self.counts, k)
-        lens, blob = ops.extract_words(self.blob_src,
-                                       self.pos.index_select(0, idx))
-        raw = bytes(blob.cpu().numpy().tobytes())
-        out = []
-        off = 0
-        for L, c in zip(lens.cpu().tolist(), cnt.cpu().tolist()):
-            out.append((raw[off:off + L], c))
-            off += L
-        return out
+        return self._pairs(cnt, self.pos.index_select(0, idx))
 
 
 class WordCountJob:

@@ -308,3 +308,149 @@ def extract_words(text: torch.Tensor, pos: torch.Tensor):
     total = int((offs[-1] + lens[-1]).item())
     blob = ext().gather_bytes(text, pos, offs, total)
     return lens, blob
+
+
+# ---------------------------------------------------------------------------
+# lexicographic order of the dictionary (sorted-result guarantee, prefix
+# queries) — runs at the finalfn / serving boundary, never in the timed job
+# ---------------------------------------------------------------------------
+
+_LEX_ROUNDS = 8  # device refinement rounds (8 bytes each) before the
+                 # still-tied residue is finished on the host; a bound on
+                 # launches, not a tuned value (MR_LEX_ROUNDS overrides)
+
+
+def _lex_host_residue(text, pos, perm, slots, seg, skip: int) -> None:
+    """Finish the strings still tied after `skip` shared bytes on the host:
+    pull only their tails, sort each tied segment, write the order back
+    into the same slots of perm.  Python's sort is stable and bytes
+    compare memcmp-then-length, which is the ordering rule."""
+    idx = perm.index_select(0, slots)
+    p = pos.index_select(0, idx)
+    tail = (((p >> 16) + skip) << 16) | ((p & 0xFFFF) - skip)
+    lens, blob = extract_words(text, tail)
+    raw = bytes(blob.cpu().numpy().tobytes())
+    idx_h = idx.cpu().tolist()
+    seg_h = seg.cpu().tolist()
+    tails = []
+    off = 0
+    for L in lens.cpu().tolist():
+        tails.append(raw[off:off + L])
+        off += L
+    out = []
+    a = 0
+    m = len(idx_h)
+    while a < m:
+        b = a
+        while b < m and seg_h[b] == seg_h[a]:
+            b += 1
+        out.extend(idx_h[j] for j in sorted(range(a, b),
+                                            key=tails.__getitem__))
+        a = b
+    perm.index_copy_(0, slots, torch.tensor(out, dtype=torch.int64,
+                                            device=perm.device))
+
+
+def lex_order(text: torch.Tensor, pos: torch.Tensor) -> torch.Tensor:
+    """-> perm i64[n] with string(perm[0]) <= string(perm[1]) <= ... in
+    byte-string lexicographic order (memcmp over the common length, then
+    the shorter first); equal strings keep ascending index order.  Strings
+    are text[off : off + len] for pos = off << 16 | len; len == 0 is legal.
+
+    MSD refinement over 8-byte big-endian chunks: a length pre-sort, one
+    full sort on chunk 0, then only elements of still-tied segments are
+    re-sorted by (segment, next chunk).  Zero-padded chunks cannot tell
+    b"a" from b"a\\x00"; the length pre-sort plus stable sorts do (see
+    NOTES.md).  One host sync per round; after MR_LEX_ROUNDS rounds
+    (default 8 = 64 shared bytes) the residue finishes on the host, so
+    one 64 KB token cannot force thousands of sorts."""
+    if not text.is_cuda:
+        from . import _cpu
+        return _cpu.lex_order(text, pos)
+    import os
+    n = pos.numel()
+    dev = pos.device
+    pos = pos.contiguous()
+    iota = torch.arange(n, dtype=torch.int64, device=dev)
+    if n < 2:
+        return iota
+    rounds = max(1, int(os.environ.get("MR_LEX_ROUNDS", _LEX_ROUNDS)))
+    e = ext()
+    empty = torch.empty(0, dtype=torch.int64, device=dev)
+    # 1. length order first: every later sort is stable, so strings whose
+    # padded chunks all tie stay shortest-first
+    lens = e.pos_len(pos)
+    _, perm = sort_by_key(lens, iota, bits=16)
+    # 2. round 0 over everything
+    keys = e.lex_chunk_keys(text, pos, perm, 0)
+    keys, perm = sort_by_key(keys, perm)
+    flags = e.head_flags(keys)
+    more = lens.index_select(0, perm) > 8
+    slots = None  # active slots of perm (None: all of them)
+    d = 0
+    while True:
+        # a segment is length-ascending, so its unfinished strings are a
+        # contiguous suffix; only runs of >= 2 of them are still unordered
+        head = flags != 0
+        prev_tied = torch.zeros_like(more)
+        prev_tied[1:] = more[:-1] & ~head[1:]
+        next_tied = torch.zeros_like(more)
+        next_tied[:-1] = more[1:] & ~head[1:]
+        act = more & (prev_tied | next_tied)
+        sel = act.nonzero().squeeze(1)  # the round's one host sync
+        m = sel.numel()
+        if m == 0:
+            return perm
+        seg_bits = max(1, int(flags.numel()).bit_length())  # seg <= size
+        seg = torch.cumsum(flags, 0).index_select(0, sel)
+        slots = sel if slots is None else slots.index_select(0, sel)
+        d += 1
+        if d >= rounds:
+            _lex_host_residue(text, pos, perm, slots, seg, 8 * d)
+            return perm
+        # 3. next chunk of the active set: stable by chunk, then by segment
+        idx = perm.index_select(0, slots)
+        keys = e.lex_chunk_keys(text, pos, idx, d)
+        keys, idx, seg = sort_by_key(keys, idx, seg)
+        seg, keys, idx = sort_by_key(seg, keys, idx, bits=seg_bits)
+        perm.index_copy_(0, slots, idx)
+        flags, more = e.lex_refine(seg, keys, pos, idx, d)
+        more = more != 0
+
+
+def lex_lower_bound(text: torch.Tensor, pos: torch.Tensor,
+                    perm: torch.Tensor, queries) -> torch.Tensor:
+    """-> i64[nq]: for each byte-string query the smallest j with
+    string(perm[j]) >= query (n if none), perm from lex_order."""
+    queries = [bytes(q) for q in queries]
+    if not text.is_cuda:
+        from . import _cpu
+        return _cpu.lex_lower_bound(text, pos, perm, queries)
+    dev = pos.device
+    offs = [0]
+    for q in queries:
+        offs.append(offs[-1] + len(q))
+    blob = b"".join(queries)
+    qblob = (torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(dev)
+             if blob else torch.empty(0, dtype=torch.uint8, device=dev))
+    qoff = torch.tensor(offs, dtype=torch.int64, device=dev)
+    return ext().lex_lower_bound(text, pos.contiguous(), perm.contiguous(),
+                                 qblob, qoff)
+
+
+def prefix_succ(p: bytes) -> Optional[bytes]:
+    """Smallest byte string greater than every string starting with p:
+    strip trailing 0xFF, increment the last byte; None = no upper bound."""
+    p = bytes(p).rstrip(b"\xff")
+    if not p:
+        return None
+    return p[:-1] + bytes([p[-1] + 1])
+
+
+def lex_prefix_range(text: torch.Tensor, pos: torch.Tensor,
+                     perm: torch.Tensor, p: bytes):
+    """-> (lo, hi): perm[lo:hi] are exactly the strings starting with p."""
+    hi_q = prefix_succ(p)
+    qs = [bytes(p)] if hi_q is None else [bytes(p), hi_q]
+    lb = lex_lower_bound(text, pos, perm, qs).tolist()
+    return lb[0], (lb[1] if hi_q is not None else int(perm.numel()))

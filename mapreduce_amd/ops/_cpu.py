@@ -137,6 +137,27 @@ def partition_counts(keys: torch.Tensor, nparts: int) -> torch.Tensor:
     return torch.from_numpy(out)
 
 
+def _strings(text: torch.Tensor, pos: torch.Tensor):
+    data = bytes(text.contiguous().numpy().tobytes())
+    return [data[p >> 16:(p >> 16) + (p & 0xFFFF)]
+            for p in _u64(pos.contiguous()).tolist()]
+
+
+def lex_order(text: torch.Tensor, pos: torch.Tensor) -> torch.Tensor:
+    words = _strings(text, pos)
+    order = sorted(range(len(words)), key=words.__getitem__)  # stable
+    return torch.tensor(order, dtype=torch.int64)
+
+
+def lex_lower_bound(text: torch.Tensor, pos: torch.Tensor,
+                    perm: torch.Tensor, queries) -> torch.Tensor:
+    import bisect
+    words = _strings(text, pos)
+    ordered = [words[j] for j in perm.tolist()]
+    return torch.tensor([bisect.bisect_left(ordered, bytes(q))
+                         for q in queries], dtype=torch.int64)
+
+
 def extract_words(text: torch.Tensor, pos: torch.Tensor):
     data = bytes(text.numpy().tobytes())
     pu = _u64(pos).tolist()

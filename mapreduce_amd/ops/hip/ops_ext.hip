@@ -12,6 +12,7 @@
 #include <limits>
 
 #include "gradsum.hip"
+#include "lex_order.hip"
 #include "mr_kernels.hip"
 #include "radix_sort.hip"
 
@@ -998,7 +999,87 @@ torch::Tensor gather_by_u32(torch::Tensor vals, torch::Tensor idx) {
   return out;
 }
 
+// ------------------------------------------------------- lexicographic order
+namespace {
+void check_text_u8(const torch::Tensor& text) {
+  // a view with a storage offset is fine (the kernels align on the
+  // absolute address); only unit stride is required
+  TORCH_CHECK(text.is_cuda() && text.scalar_type() == torch::kUInt8 &&
+              text.dim() == 1 && text.is_contiguous(),
+              "text must be contiguous 1-D u8 on GPU");
+}
+}  // namespace
+
+// keys[i] = big-endian chunk d of string idx[i] (idx empty: identity)
+torch::Tensor lex_chunk_keys(torch::Tensor text, torch::Tensor pos,
+                             torch::Tensor idx, long d) {
+  check_text_u8(text);
+  check_dev_i64(pos, "pos");
+  bool has_idx = idx.numel() > 0;
+  if (has_idx) check_dev_i64(idx, "idx");
+  TORCH_CHECK(d >= 0 && d < 8192, "chunk index out of range");
+  long m = has_idx ? idx.numel() : pos.numel();
+  auto out = torch::empty({m}, pos.options());
+  if (m)
+    hipLaunchKernelGGL(lex_chunk_keys_kernel, dim3(grid_for(m)), dim3(kBlock),
+                       0, cur_stream(), text.data_ptr<u8>(), text.numel(),
+                       u64cp(pos), has_idx ? idx.data_ptr<i64>() : nullptr, m,
+                       d, u64p(out));
+  return out;
+}
+
+// -> (head flags, "string continues past chunk d" flags) of the active set
+std::vector<torch::Tensor> lex_refine(torch::Tensor seg, torch::Tensor keys,
+                                      torch::Tensor pos, torch::Tensor idx,
+                                      long d) {
+  check_dev_i64(seg, "seg");
+  check_dev_i64(keys, "keys");
+  check_dev_i64(pos, "pos");
+  check_dev_i64(idx, "idx");
+  long m = keys.numel();
+  TORCH_CHECK(seg.numel() == m && idx.numel() == m,
+              "seg, keys and idx must have one entry per active element");
+  auto flags = torch::empty({m}, keys.options());
+  auto more = torch::empty({m}, keys.options());
+  if (m)
+    hipLaunchKernelGGL(lex_refine_kernel, dim3(grid_for(m)), dim3(kBlock), 0,
+                       cur_stream(), seg.data_ptr<i64>(), u64cp(keys),
+                       u64cp(pos), idx.data_ptr<i64>(), m, d,
+                       flags.data_ptr<i64>(), more.data_ptr<i64>());
+  return {flags, more};
+}
+
+// out[q] = first j with string(perm[j]) >= query q; queries packed in
+// qblob with offsets qoff[nq + 1]
+torch::Tensor lex_lower_bound(torch::Tensor text, torch::Tensor pos,
+                              torch::Tensor perm, torch::Tensor qblob,
+                              torch::Tensor qoff) {
+  check_text_u8(text);
+  check_dev_i64(pos, "pos");
+  check_dev_i64(perm, "perm");
+  check_dev_i64(qoff, "qoff");
+  TORCH_CHECK(qblob.is_cuda() && qblob.scalar_type() == torch::kUInt8 &&
+              qblob.is_contiguous(), "qblob must be contiguous u8 on GPU");
+  TORCH_CHECK(perm.numel() == pos.numel(), "perm must permute pos");
+  TORCH_CHECK(qoff.numel() >= 1, "qoff holds nq + 1 offsets");
+  long nq = qoff.numel() - 1;
+  auto out = torch::empty({nq}, pos.options());
+  if (nq)
+    hipLaunchKernelGGL(lex_lower_bound_kernel, dim3(grid_for(nq)),
+                       dim3(kBlock), 0, cur_stream(), text.data_ptr<u8>(),
+                       text.numel(), u64cp(pos), perm.data_ptr<i64>(),
+                       perm.numel(), qblob.data_ptr<u8>(),
+                       qoff.data_ptr<i64>(), nq, out.data_ptr<i64>());
+  return out;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("lex_chunk_keys", &lex_chunk_keys,
+        "big-endian 8-byte chunk d of each string as a sortable u64");
+  m.def("lex_refine", &lex_refine,
+        "(seg, key) head flags + unfinished-string flags");
+  m.def("lex_lower_bound", &lex_lower_bound,
+        "binary search of byte-string queries in a lex permutation");
   m.def("radix_sort_idx32", &radix_sort_idx32,
         "sort u64 keys with a u32 iota payload -> (keys, perm)");
   m.def("gather_by_u32", &gather_by_u32, "out[i] = vals[idx[i]] (u32 idx)");

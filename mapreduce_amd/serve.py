@@ -15,6 +15,8 @@ Endpoints:
     GET /healthz                     liveness + which results are mounted
     GET /count?word=the              count of one word (binary search)
     GET /topk?k=10                   k most frequent words
+    GET /prefix?p=inter&limit=20     words starting with p, lexicographic
+                                     (device lower bounds on lex_perm)
     GET /postings?word=the           inverted-index postings [(doc, tf)]
 """
 
@@ -56,6 +58,14 @@ def make_app(wordcount=None, index=None):
         res = _wc()
         return {"topk": [{"word": w.decode("utf-8", "replace"), "count": c}
                          for w, c in res.topk(k)]}
+
+    @app.get("/prefix")
+    def prefix(p: str = "", limit: int = 20):
+        res = _wc()
+        pb = p.encode()
+        return {"prefix": p, "total": res.count_prefix(pb),
+                "words": [{"word": w.decode("utf-8", "replace"), "count": c}
+                          for w, c in res.prefix(pb, limit)]}
 
     @app.get("/postings")
     def postings(word: str):
