@@ -652,6 +652,18 @@ __global__ __launch_bounds__(256) void tokenize_v5_kernel(
 // extra barriers/LDS cost more than lane balance buys.
 // ---------------------------------------------------------------------------
 
+// (pos << 16 | len) of the word at the lowest set bit of `smw` (the
+// not-yet-consumed starts of a 16-byte window): len is the distance to the
+// next whitespace bit of m32, or `long_len` when the word runs past the
+// 32-byte register window (only a window's last start can).
+__device__ __forceinline__ u64 v6_spill_pos(u64 wpos0, u32 smw, u32 m32,
+                                            u32 long_len) {
+  int s = __ffs(smw) - 1;
+  u32 t = m32 >> s;
+  u32 len = t ? (u32)(__ffs(t) - 1) : long_len;
+  return ((wpos0 + (u64)s) << 16) | (u64)len;
+}
+
 // MODE (ablation, §5.4 rule 8): 0=full, 1=stage+classify, 2=+hash, 3=+cache (no spill)
 template <int CACHE_N, bool GPOS, int TILE_N, int MODE = 0,
           bool SPILL_ALL = false,  // emit every word (no cache)
@@ -754,8 +766,14 @@ __global__ __launch_bounds__(BLOCKN) void tokenize_v6_kernel(
     // (measured 2.7 ms of a 3.2 ms kernel, ablation modes 3 vs 4), and
     // per-word ballot aggregation is worse still (12.8 ms: divergent
     // ballots + atomics)
+    // Only the keys are buffered: a spilled record's position is rebuilt
+    // where it is stored (v6_spill_pos) from the start mask, m32 and the
+    // one long-word length — 16 fewer VGPRs (106 -> 90 on the word-count
+    // default, which admits 5 waves/SIMD instead of 4).
     u64 sh_[8];
-    u64 sp_[8];
+    const u32 sm0 = sm;
+    u32 long_len = 0;  // len of the (at most one, last) word past the window
+    const u64 wpos0 = pos_base + (u64)(base + my0);
     u32 miss_mask = 0;
     #pragma unroll
     for (int wi = 0; wi < 8; ++wi) {
@@ -802,6 +820,7 @@ __global__ __launch_bounds__(BLOCKN) void tokenize_v6_kernel(
         if (cb) h = whash_chunk(h, chunk);
         h = whash_fin(h, (u64)wlen);
         len = (u32)(wlen > 0xFFFF ? 0xFFFF : wlen);
+        long_len = len;
       }
       if (MODE == 2) { my_words += h; continue; }
       if (COMPOSITE) {
@@ -816,7 +835,6 @@ __global__ __launch_bounds__(BLOCKN) void tokenize_v6_kernel(
       if (SPILL_ALL) {
         miss_mask |= 1u << wi;
         sh_[wi] = k;
-        sp_[wi] = p;
         continue;
       }
       // LDS cache insert
@@ -848,7 +866,6 @@ __global__ __launch_bounds__(BLOCKN) void tokenize_v6_kernel(
         } else {
           miss_mask |= 1u << wi;  // wi is compile-time: register slot
           sh_[wi] = k;
-          sp_[wi] = p;
         }
       }
     }
@@ -862,12 +879,15 @@ __global__ __launch_bounds__(BLOCKN) void tokenize_v6_kernel(
       // that motivated the chunked allocator does not apply), writes of a
       // round's same-bucket members are adjacent, and no pad entries exist
       // — counters are exact per-bucket lengths.
+      u32 smw = sm0;
       #pragma unroll
       for (int wi = 0; wi < 8; ++wi) {
         unsigned long long pending =
             __ballot((miss_mask >> wi) & 1u);
         if (__ballot(miss_mask >> wi) == 0) break;  // no lane has more slots
         bool mine = (miss_mask >> wi) & 1u;
+        u64 mypos = mine ? v6_spill_pos(wpos0, smw, m32, long_len) : 0;
+        smw &= smw - 1;
         u64 bk = mine ? (sh_[wi] >> 56) % (u64)NBKT : 0;
         int lane = threadIdx.x & (WAVE - 1);
         unsigned long long lt_mask =
@@ -888,7 +908,7 @@ __global__ __launch_bounds__(BLOCKN) void tokenize_v6_kernel(
             if (r < spill_cap) {  // overflow: counter runs past cap — the
               long o = (long)lead_bk * spill_cap + r;  // host detects
               out_hash[o] = sh_[wi];                   // max(cnt) > cap
-              out_pos[o] = sp_[wi];
+              out_pos[o] = mypos;
             }
           }
           pending &= ~members;
@@ -896,6 +916,8 @@ __global__ __launch_bounds__(BLOCKN) void tokenize_v6_kernel(
       }
     } else {
       u32 my_ns = (u32)__popc(miss_mask);
+      // (four ballots + mbcnt instead of these six dependent shuffles
+      // measured no gain: profiles/tokenizer_occupancy_r04.md)
       u32 incl = my_ns;
       #pragma unroll
       for (int off = 1; off < WAVE; off <<= 1) {
@@ -923,17 +945,20 @@ __global__ __launch_bounds__(BLOCKN) void tokenize_v6_kernel(
         wchunk += wave_total;
         wleft -= (int)wave_total;
       }
+      u32 smw = sm0;
       #pragma unroll
       for (int wi = 0; wi < 8; ++wi) {
         if (miss_mask & (1u << wi)) {
+          u64 p = v6_spill_pos(wpos0, smw, m32, long_len);
           if (MODE == 4) {
-            my_words += sh_[wi] + sp_[wi] + (u64)o;
+            my_words += sh_[wi] + p + (u64)o;
           } else if (o < spill_cap) {
             out_hash[o] = sh_[wi];
-            out_pos[o] = sp_[wi];
+            out_pos[o] = p;
           }
           ++o;
         }
+        smw &= smw - 1;
       }
     }
     }  // wnd

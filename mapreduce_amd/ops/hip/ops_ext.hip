@@ -10,6 +10,9 @@
 #include <torch/extension.h>
 
 #include <limits>
+#include <map>
+#include <mutex>
+#include <utility>
 
 #include "gradsum.hip"
 #include "lex_order.hip"
@@ -29,6 +32,58 @@ long grid_for(long n, long per_thread = 1) {
 }
 
 hipStream_t cur_stream() { return at::hip::getCurrentHIPStream(); }
+
+// Grid of the LDS-cached tokenizer launches.  Every block carries fixed
+// costs (a cold word cache, an end-of-kernel flush of that cache into the
+// global table, one stranded spill chunk per wave), and whatever it leaves
+// free on a CU is what the drain kernels of the previous job run in when
+// jobs are pipelined.  So the grid is ONE round of at most kTokWavesPerCu
+// waves per CU, never more blocks than the kernel's registers + LDS admit
+// (occupancy query, once per instantiation and device), never more than
+// kMaxBlocks (the spill slack and the cpos side buffers are sized for
+// that many).  Measured on the bench shape, pipelined ms/step: 1024
+// blocks 1.29-1.35, 2048 (the old fixed grid) 1.37-1.44, 768 1.39-1.42,
+// 1280 (all the query admits) 1.38-1.42, 1536 1.48-1.49 — the grid also
+// sets total cache capacity and how many 2048-entry spill chunks a wave
+// strands (profiles/tokenizer_occupancy_r04.md).
+constexpr int kTokWavesPerCu = 16;
+
+struct TokOccupancy {
+  int blocks_per_cu = 0;
+  int cus = 0;
+};
+
+TokOccupancy tok_occupancy(const void* kfn, int blockn) {
+  static std::mutex mu;
+  static std::map<std::pair<const void*, int>, TokOccupancy> cache;
+  int dev = 0;
+  C10_HIP_CHECK(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = cache.find({kfn, dev});
+  if (it != cache.end()) return it->second;
+  TokOccupancy o;
+  C10_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+      &o.blocks_per_cu, kfn, blockn, 0));
+  C10_HIP_CHECK(hipDeviceGetAttribute(
+      &o.cus, hipDeviceAttributeMultiprocessorCount, dev));
+  TORCH_CHECK(o.blocks_per_cu > 0 && o.cus > 0,
+              "tokenizer occupancy query returned ", o.blocks_per_cu,
+              " blocks/CU on ", o.cus, " CUs");
+  cache[{kfn, dev}] = o;
+  return o;
+}
+
+template <typename K>
+long tok_grid(K kfn, int blockn, long n, long tile_bytes) {
+  long tiles = (n + tile_bytes - 1) / tile_bytes;
+  if (tiles < 1) tiles = 1;
+  TokOccupancy o = tok_occupancy(reinterpret_cast<const void*>(kfn), blockn);
+  int per_cu = kTokWavesPerCu / (blockn / WAVE);
+  if (per_cu > o.blocks_per_cu) per_cu = o.blocks_per_cu;
+  long resident = (long)per_cu * o.cus;
+  long blocks = tiles < resident ? tiles : resident;
+  return blocks < kMaxBlocks ? blocks : kMaxBlocks;
+}
 
 // LDS-staged scatter (v2) is the default — direct scatter (v1) measured
 // ~2.5x slower on write coalescing; MR_RADIX_V1=1 switches back for A/B.
@@ -177,6 +232,10 @@ std::vector<torch::Tensor> tokenize_spill_v2(torch::Tensor text,
     // 512 already amortizes reservations per-entry; 2048 quadruples the
     // padded chunk tails flowing through radix+bucket (measured 12.4 vs
     // 9.9 ms on the inverted-index job)
+    // spill-all keeps the kMaxBlocks-capped grid: it has no per-block
+    // cache to warm or flush, and the inverted index measured 8.05-8.08
+    // ms/job on the one-round grid vs 8.03-8.06 on this one (parent
+    // 8.02-8.07; profiles/tokenizer_occupancy_r04.md)
     hipLaunchKernelGGL((tokenize_v6_kernel<16, false, 4096, 0, true>),
                        dim3(grid_for(n, TOK_BYTES)), dim3(kBlock), 0,
                        cur_stream(), text.data_ptr<u8>(), n, (u64)pos_base,
@@ -238,7 +297,9 @@ void tokenize_cache_spill_composite(
   TORCH_CHECK(out_hash.numel() >= spill_cap && out_pos.numel() >= spill_cap,
               "spill arrays too small");
   if (!n) return;
-  long blocks = grid_for(n, TOK_BYTES);
+  auto kfn =
+      tokenize_v6_kernel<2048, true, 4096, 0, false, true, 2048, 0, 256>;
+  long blocks = tok_grid(kfn, kBlock, n, 4096);
   static torch::Tensor cpos_gc;  // persistent GPOS side-buffer
   long need = blocks * 2048;
   if (!cpos_gc.defined() || cpos_gc.numel() < need ||
@@ -247,8 +308,7 @@ void tokenize_cache_spill_composite(
                                         .device(text.device())
                                         .dtype(torch::kInt64));
   hipLaunchKernelGGL(
-      (tokenize_v6_kernel<2048, true, 4096, 0, false, true, 2048, 0, 256>),
-      dim3(blocks), dim3(kBlock), 0, cur_stream(), text.data_ptr<u8>(), n,
+      kfn, dim3(blocks), dim3(kBlock), 0, cur_stream(), text.data_ptr<u8>(), n,
       (u64)pos_base, u64p(tkeys), tvals.data_ptr<i64>(),
       texm.numel() ? u64p(texm) : nullptr, (u64)(cap - 1), u64p(out_hash),
       u64p(out_pos),
@@ -347,7 +407,7 @@ void tokenize_cache_spill(
       else if (cache == 1024) kfn = tokenize_v6_kernel<1024, false, 4096>;
       else if (schunk == 128)
         kfn = tokenize_v6_kernel<2048, false, 4096, 0, false, false, 128>;
-      long blocks = grid_for(n, TOK_BYTES * (tsz / 4096));
+      long blocks = tok_grid(kfn, blockn, n, tsz);
       static torch::Tensor cpos_g;  // persistent side-buffer (GPOS only)
       u64* cpg = nullptr;
       if (gpos) {
@@ -418,7 +478,7 @@ void tokenize_cache_spill_bucketed(
   auto kfn = tokenize_v6_kernel<2048, false, 4096, 0, false, false, 512, 256>;
   if (gpos)
     kfn = tokenize_v6_kernel<2048, true, 4096, 0, false, false, 512, 256>;
-  long blocks = grid_for(n, TOK_BYTES);
+  long blocks = tok_grid(kfn, kBlock, n, 4096);
   static torch::Tensor cpos_gb;  // persistent GPOS side-buffer
   u64* cpg = nullptr;
   if (gpos) {
@@ -454,13 +514,13 @@ double tok6_ablate(torch::Tensor text, long mode, long iters) {
   auto op = torch::empty({cap}, opts);
   auto ctr = torch::zeros({1}, opts);
   auto nw = torch::zeros({1}, opts);
-  long blocks = grid_for(n, TOK_BYTES);
-  auto cpg = torch::empty({blocks * 2048}, opts);
   auto kfn = tokenize_v6_kernel<2048, true, 4096, 0>;
   if (mode == 1) kfn = tokenize_v6_kernel<2048, true, 4096, 1>;
   else if (mode == 2) kfn = tokenize_v6_kernel<2048, true, 4096, 2>;
   else if (mode == 3) kfn = tokenize_v6_kernel<2048, true, 4096, 3>;
   else if (mode == 4) kfn = tokenize_v6_kernel<2048, true, 4096, 4>;
+  long blocks = tok_grid(kfn, kBlock, n, 4096);
+  auto cpg = torch::empty({blocks * 2048}, opts);
   hipStream_t st = cur_stream();
   hipEvent_t e0, e1;
   hipEventCreate(&e0);
@@ -1073,7 +1133,25 @@ torch::Tensor lex_lower_bound(torch::Tensor text, torch::Tensor pos,
   return out;
 }
 
+// Occupancy of the default word-count tokenizer instantiation on the
+// current device, as the runtime sees it (blocks/CU clips the grid; the
+// register count and static LDS are what decide it).
+py::dict tokenizer_occupancy() {
+  auto kfn = tokenize_v6_kernel<2048, true, 4096, 0, false, false, 2048>;
+  TokOccupancy o = tok_occupancy(reinterpret_cast<const void*>(kfn), kBlock);
+  hipFuncAttributes fa;
+  C10_HIP_CHECK(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kfn)));
+  py::dict d;
+  d["blocks_per_cu"] = o.blocks_per_cu;
+  d["cus"] = o.cus;
+  d["num_regs"] = fa.numRegs;
+  d["lds_bytes"] = (long)fa.sharedSizeBytes;
+  return d;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("tokenizer_occupancy", &tokenizer_occupancy,
+        "blocks/CU, registers and static LDS of the default tokenizer");
   m.def("lex_chunk_keys", &lex_chunk_keys,
         "big-endian 8-byte chunk d of each string as a sortable u64");
   m.def("lex_refine", &lex_refine,
