@@ -21,12 +21,17 @@ Pipeline per rank (GPU):
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import List, Optional, Tuple
+from typing import List, NamedTuple, Optional, Tuple
 
 import torch
 
 from .. import ops
 from . import dist as dx
+
+
+class SearchResult(NamedTuple):
+    hits: int    # documents matching the query (not capped by k)
+    docs: list   # [(doc, score), ...] best first, at most k
 
 
 @dataclass
@@ -40,6 +45,8 @@ class InvertedIndexResult:
     hash_kind: str = "wordhash64"  # GPU tier: wordhash64 (ops/hip
                                    # common.h); CPU test tier: fnv1a64
                                    # (ops/_cpu.py tokenize_words)
+    ndocs: Optional[int] = None  # documents indexed (the N of tf-idf);
+                                 # None when the job ran on several ranks
 
     def to_host(self):
         lens, blob = ops.extract_words(self.blob_src, self.pos)
@@ -127,9 +134,8 @@ class InvertedIndexResult:
             self._sk = sk
         return sk
 
-    def lookup(self, word) -> list:
-        """Serve one word's postings [(doc, tf), ...] — O(log n) binary
-        search on the hash-sorted index, no host materialization."""
+    def _term_hash(self, word) -> int:
+        """The word's key as the i64 bit pattern stored in keys."""
         if isinstance(word, str):
             word = word.encode()
         if self.hash_kind == "wordhash64":
@@ -139,7 +145,12 @@ class InvertedIndexResult:
             k = 0xCBF29CE484222325
             for b in word:
                 k = ((k ^ b) * 0x100000001B3) & 0xFFFFFFFFFFFFFFFF
-        ki = k - (1 << 64) if k >= (1 << 63) else k
+        return k - (1 << 64) if k >= (1 << 63) else k
+
+    def lookup(self, word) -> list:
+        """Serve one word's postings [(doc, tf), ...] — O(log n) binary
+        search on the hash-sorted index, no host materialization."""
+        ki = self._term_hash(word)
         sk = self._signed_keys()
         q = torch.tensor([ki ^ (-1 << 63)], dtype=torch.int64,
                          device=sk.device)
@@ -150,6 +161,92 @@ class InvertedIndexResult:
         o1 = int(self.doc_offsets[i + 1].item())
         return list(zip(self.docs[o0:o1].cpu().tolist(),
                         self.tf[o0:o1].cpu().tolist()))
+
+    def idf_weights(self, ndocs: Optional[int] = None) -> torch.Tensor:
+        """i64[nwords] fixed-point idf, w = rint(65536 * ln(1 + N / df)),
+        df = the word's document count.  Computed on the host in f64 from
+        one readback of df and uploaded, so both tiers hold the same
+        integers; cached per N."""
+        n = self.ndocs if ndocs is None else ndocs
+        if n is None:
+            raise ValueError(
+                "tfidf scoring needs the document count: this index has no "
+                "ndocs (built on several ranks); pass ndocs=")
+        n = int(n)
+        cache = self.__dict__.setdefault("_idf", {})
+        w = cache.get(n)
+        if w is None:
+            import numpy as np
+            df = getattr(self, "_df_host", None)
+            if df is None:
+                df = np.diff(self.doc_offsets.cpu().numpy()).astype(
+                    np.float64)
+                self._df_host = df
+            wh = np.rint(65536.0 * np.log(1.0 + n / df)).astype(np.int64)
+            w = torch.from_numpy(wh).to(self.keys.device)
+            cache[n] = w
+        return w
+
+    @staticmethod
+    def _terms(query) -> list:
+        """A query as a list of distinct byte-string terms: str/bytes are
+        split on whitespace, sequences taken as they are; duplicates
+        dropped, first occurrence kept."""
+        if isinstance(query, (str, bytes)):
+            query = query.split()
+        out, seen = [], set()
+        for t in query:
+            if isinstance(t, str):
+                t = t.encode()
+            t = bytes(t)
+            if t not in seen:
+                seen.add(t)
+                out.append(t)
+        return out
+
+    def search_batch(self, queries, mode: str = "and", k: int = 10,
+                     scoring: str = "tf", ndocs: Optional[int] = None
+                     ) -> List[SearchResult]:
+        """Ranked search of many queries at once: one ops.postings_search
+        call, two uploads (term hashes, offsets) and one readback whatever
+        the number of queries.  See search()."""
+        if scoring == "tf":
+            weights = None
+        elif scoring == "tfidf":
+            weights = self.idf_weights(ndocs)
+        else:
+            raise ValueError(
+                f"scoring must be 'tf' or 'tfidf', got {scoring!r}")
+        hashes, offs = [], [0]
+        for query in queries:
+            hashes.extend(self._term_hash(t) for t in self._terms(query))
+            offs.append(len(hashes))
+        out = ops.postings_search(
+            self.keys, self.doc_offsets, self.docs, self.tf, weights,
+            torch.tensor(hashes, dtype=torch.int64),
+            torch.tensor(offs, dtype=torch.int64), k, mode)
+        d, s, n, h = out
+        k = d.shape[1]
+        host = torch.cat([d, s, n[:, None], h[:, None]], dim=1).cpu().tolist()
+        return [SearchResult(row[2 * k + 1],
+                             list(zip(row[:row[2 * k]],
+                                      row[k:k + row[2 * k]])))
+                for row in host]
+
+    def search(self, terms, mode: str = "and", k: int = 10,
+               scoring: str = "tf", ndocs: Optional[int] = None
+               ) -> SearchResult:
+        """Documents matching a multi-term query, best first.
+
+        terms: a str/bytes split on whitespace, or a sequence of terms.
+        mode "and": documents holding every term; "or": at least one.
+        scoring "tf": score = sum of the matching terms' frequencies;
+        "tfidf": each weighted by idf_weights(ndocs).  Equal scores order
+        by ascending doc id.  -> SearchResult(hits, [(doc, score), ...])
+        with at most k documents; hits counts all matches.  This rank's
+        index only (words are hash-partitioned across ranks)."""
+        return self.search_batch([terms], mode=mode, k=k, scoring=scoring,
+                                 ndocs=ndocs)[0]
 
 
 _SM64_C0 = 0x9E3779B97F4A7C15 - (1 << 64)
@@ -420,4 +517,5 @@ class InvertedIndexJob:
         return InvertedIndexResult(
             keys=wk, doc_offsets=offsets, docs=ud, tf=tf, pos=wpos,
             blob_src=blob_src,
-            hash_kind="wordhash64" if dev.type == "cuda" else "fnv1a64")
+            hash_kind="wordhash64" if dev.type == "cuda" else "fnv1a64",
+            ndocs=self.doc_base + len(splits) if self.world == 1 else None)

@@ -454,3 +454,77 @@ def lex_prefix_range(text: torch.Tensor, pos: torch.Tensor,
     qs = [bytes(p)] if hi_q is None else [bytes(p), hi_q]
     lb = lex_lower_bound(text, pos, perm, qs).tolist()
     return lb[0], (lb[1] if hi_q is not None else int(perm.numel()))
+
+
+# ---------------------------------------------------------------------------
+# ranked multi-term search over the inverted index (serving path, never in
+# the timed job)
+# ---------------------------------------------------------------------------
+
+# caps of the postings_search kernel (ops/hip/postings_query.hip): terms per
+# query, k, LDS candidate buffer.  The CPU tier has no such limits of its
+# own; it keeps the same interface so both tiers accept the same queries.
+POSTINGS_TMAX = 16
+POSTINGS_KMAX = 256
+POSTINGS_BUF = 2048
+
+_POSTINGS_MODES = {"and": 0, "or": 1}
+
+
+def postings_search_caps():
+    """-> (TMAX, KMAX, BUF): the extension's own values on a GPU machine,
+    the Python constants above on the CPU tier."""
+    if torch.cuda.is_available():
+        return tuple(int(c) for c in ext().postings_search_caps())
+    return POSTINGS_TMAX, POSTINGS_KMAX, POSTINGS_BUF
+
+
+def postings_search(keys: torch.Tensor, doc_offsets: torch.Tensor,
+                    docs: torch.Tensor, tf: torch.Tensor,
+                    weights: Optional[torch.Tensor], qkeys: torch.Tensor,
+                    qoff: torch.Tensor, k: int, mode: str = "and"):
+    """Ranked search of a batch of queries over the CSR index (keys sorted
+    u64 bits, doc_offsets[nwords + 1] into docs/tf, docs ascending and
+    unique per word).  Query q is the term hashes qkeys[qoff[q]:qoff[q+1]].
+
+    mode "and": docs in every term's list (unknown term or no terms: none);
+    "or": docs in at least one.  score = sum over the query's terms present
+    of tf * weights[term row] (weights None or empty: all 1), i64.  Order:
+    score descending, doc ascending on equal score.
+
+    -> (docs i64[nq, k], scores i64[nq, k], n i64[nq] = min(k, hits),
+    hits i64[nq]); unused slots hold doc = -1, score = 0.
+
+    qkeys/qoff may live on the host: they are checked there and uploaded
+    (two uploads); device-resident ones cost one readback of qoff for the
+    check.  Nothing else synchronizes."""
+    tmax, kmax, _ = postings_search_caps()
+    if mode not in _POSTINGS_MODES:
+        raise ValueError(f"mode must be 'and' or 'or', got {mode!r}")
+    k = int(k)
+    if not 1 <= k <= kmax:
+        raise ValueError(f"k must be in [1, {kmax}], got {k}")
+    if qoff.numel() < 1:
+        raise ValueError("qoff holds nq + 1 offsets")
+    qo = qoff.cpu()
+    if qo.numel() > 1:
+        per = qo[1:] - qo[:-1]
+        if int(per.min()) < 0 or int(qo[0]) < 0 \
+                or int(qo[-1]) > qkeys.numel():
+            raise ValueError("qoff must ascend within qkeys")
+        if int(per.max()) > tmax:
+            raise ValueError(
+                f"at most {tmax} terms per query, got {int(per.max())}")
+    dev = keys.device
+    if weights is None:
+        weights = torch.empty(0, dtype=torch.int64, device=dev)
+    if not keys.is_cuda:
+        from . import _cpu
+        return _cpu.postings_search(keys, doc_offsets, docs, tf, weights,
+                                    qkeys.cpu(), qo, k,
+                                    _POSTINGS_MODES[mode])
+    return tuple(ext().postings_search(
+        keys.contiguous(), doc_offsets.contiguous(), docs.contiguous(),
+        tf.contiguous(), weights.contiguous(),
+        qkeys.to(dev).contiguous(), qoff.to(dev).contiguous(), k,
+        _POSTINGS_MODES[mode]))

@@ -171,3 +171,61 @@ def extract_words(text: torch.Tensor, pos: torch.Tensor):
     return (torch.tensor(lens, dtype=torch.int64),
             torch.from_numpy(np.frombuffer(blob, dtype=np.uint8).copy())
             if blob else torch.empty(0, dtype=torch.uint8))
+
+
+def postings_search(keys, doc_offsets, docs, tf, weights, qkeys, qoff,
+                    k: int, mode: int):
+    """NumPy form of the postings_search kernel (same outputs, bit for
+    bit): per query, AND/OR of the terms' doc lists, score = sum of
+    tf * weight over the terms present (wrapping i64), best k by score
+    descending then doc ascending.  mode: 0 = AND, 1 = OR."""
+    ku = _u64(keys.contiguous())
+    offs = doc_offsets.contiguous().numpy()
+    dn = docs.contiguous().numpy()
+    tn = tf.contiguous().numpy()
+    wn = weights.contiguous().numpy() if weights.numel() else None
+    qk = _u64(qkeys.contiguous())
+    qo = qoff.contiguous().numpy()
+    nq = len(qo) - 1
+    out_docs = np.full((nq, k), -1, dtype=np.int64)
+    out_scores = np.zeros((nq, k), dtype=np.int64)
+    out_n = np.zeros(nq, dtype=np.int64)
+    out_hits = np.zeros(nq, dtype=np.int64)
+    for q in range(nq):
+        lists = []  # per term (docs, tf * weight); unknown term = empty
+        for h in qk[qo[q]:qo[q + 1]]:
+            r = int(np.searchsorted(ku, h))
+            if r < len(ku) and ku[r] == h:
+                a, b = int(offs[r]), int(offs[r + 1])
+                w = np.int64(wn[r] if wn is not None else 1)
+                lists.append((dn[a:b], tn[a:b] * w))
+            else:
+                lists.append((dn[:0], tn[:0]))
+        if not lists:
+            continue
+        if mode == 0:
+            lens = [len(d) for d, _ in lists]
+            cand = lists[lens.index(min(lens))][0]
+        else:
+            cand = np.unique(np.concatenate([d for d, _ in lists]))
+        keep = np.ones(len(cand), dtype=bool)
+        score = np.zeros(len(cand), dtype=np.int64)
+        for d, s in lists:
+            if len(d) == 0:
+                found = np.zeros(len(cand), dtype=bool)
+            else:
+                p = np.minimum(np.searchsorted(d, cand), len(d) - 1)
+                found = d[p] == cand
+                score = score + np.where(found, s[p], 0)
+            if mode == 0:
+                keep &= found
+        cand, score = cand[keep], score[keep]
+        # score descending (~s = -s - 1: no overflow), doc ascending on ties
+        order = np.lexsort((cand, ~score))
+        n = min(k, len(cand))
+        out_hits[q] = len(cand)
+        out_n[q] = n
+        out_docs[q, :n] = cand[order[:n]]
+        out_scores[q, :n] = score[order[:n]]
+    return (torch.from_numpy(out_docs), torch.from_numpy(out_scores),
+            torch.from_numpy(out_n), torch.from_numpy(out_hits))

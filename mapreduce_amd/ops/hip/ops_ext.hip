@@ -17,6 +17,7 @@
 #include "gradsum.hip"
 #include "lex_order.hip"
 #include "mr_kernels.hip"
+#include "postings_query.hip"
 #include "radix_sort.hip"
 
 namespace {
@@ -1133,6 +1134,57 @@ torch::Tensor lex_lower_bound(torch::Tensor text, torch::Tensor pos,
   return out;
 }
 
+// ------------------------------------------------------- ranked index search
+// caps of postings_search: (terms per query, k, LDS candidate buffer)
+std::vector<long> postings_search_caps() {
+  return {PQ_TMAX, PQ_KMAX, PQ_BUF};
+}
+
+// One block per query over the CSR index; queries packed in qkeys with
+// offsets qoff[nq + 1].  -> (docs[nq, k], scores[nq, k], n[nq], hits[nq]);
+// unused slots hold doc = -1, score = 0.  weights: i64[nwords] or empty
+// (= all 1).  mode: 0 = AND, 1 = OR.  No host sync.
+std::vector<torch::Tensor> postings_search(
+    torch::Tensor keys, torch::Tensor doc_offsets, torch::Tensor docs,
+    torch::Tensor tf, torch::Tensor weights, torch::Tensor qkeys,
+    torch::Tensor qoff, long k, long mode) {
+  check_dev_i64(keys, "keys");
+  check_dev_i64(doc_offsets, "doc_offsets");
+  check_dev_i64(docs, "docs");
+  check_dev_i64(tf, "tf");
+  check_dev_i64(qkeys, "qkeys");
+  check_dev_i64(qoff, "qoff");
+  bool has_w = weights.numel() > 0;
+  if (has_w) check_dev_i64(weights, "weights");
+  long nwords = keys.numel();
+  TORCH_CHECK(doc_offsets.numel() == nwords + 1,
+              "doc_offsets holds nwords + 1 offsets");
+  TORCH_CHECK(tf.numel() == docs.numel(), "tf must have one entry per doc");
+  TORCH_CHECK(!has_w || weights.numel() == nwords,
+              "weights must be empty or one per word");
+  TORCH_CHECK(qoff.numel() >= 1, "qoff holds nq + 1 offsets");
+  TORCH_CHECK(k >= 1 && k <= PQ_KMAX, "k must be in [1, ", PQ_KMAX, "]");
+  TORCH_CHECK(mode == PQ_MODE_AND || mode == PQ_MODE_OR,
+              "mode must be 0 (AND) or 1 (OR)");
+  long nq = qoff.numel() - 1;
+  auto opts = keys.options();
+  auto out_docs = torch::empty({nq, k}, opts);
+  auto out_scores = torch::empty({nq, k}, opts);
+  auto out_n = torch::empty({nq}, opts);
+  auto out_hits = torch::empty({nq}, opts);
+  if (nq)
+    hipLaunchKernelGGL(postings_search_kernel, dim3(nq), dim3(PQ_BLOCK), 0,
+                       cur_stream(), u64cp(keys), nwords,
+                       doc_offsets.data_ptr<i64>(), docs.data_ptr<i64>(),
+                       tf.data_ptr<i64>(), docs.numel(),
+                       has_w ? weights.data_ptr<i64>() : nullptr,
+                       u64cp(qkeys), qkeys.numel(), qoff.data_ptr<i64>(),
+                       (int)k, (int)mode, out_docs.data_ptr<i64>(),
+                       out_scores.data_ptr<i64>(), out_n.data_ptr<i64>(),
+                       out_hits.data_ptr<i64>());
+  return {out_docs, out_scores, out_n, out_hits};
+}
+
 // Occupancy of the default word-count tokenizer instantiation on the
 // current device, as the runtime sees it (blocks/CU clips the grid; the
 // register count and static LDS are what decide it).
@@ -1152,6 +1204,10 @@ py::dict tokenizer_occupancy() {
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("tokenizer_occupancy", &tokenizer_occupancy,
         "blocks/CU, registers and static LDS of the default tokenizer");
+  m.def("postings_search", &postings_search,
+        "ranked AND/OR top-k over the inverted index, one block per query");
+  m.def("postings_search_caps", &postings_search_caps,
+        "(TMAX, KMAX, BUF) of postings_search");
   m.def("lex_chunk_keys", &lex_chunk_keys,
         "big-endian 8-byte chunk d of each string as a sortable u64");
   m.def("lex_refine", &lex_refine,

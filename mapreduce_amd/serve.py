@@ -4,7 +4,7 @@ materializing it.
 The reference's consumption story ends at finalfn / result files
 (server.lua:348-385: read every result.P file to do anything).  On the
 GPU tier results are HBM-resident and indexed, so point queries are
-device-side lookups (InvertedIndexResult.lookup, WordCountResult.topk)
+device-side lookups (InvertedIndexResult.lookup / search, WordCountResult.topk)
 — this module exposes them over HTTP for serving deployments:
 
     from mapreduce_amd.serve import make_app
@@ -18,6 +18,11 @@ Endpoints:
     GET /prefix?p=inter&limit=20     words starting with p, lexicographic
                                      (device lower bounds on lex_perm)
     GET /postings?word=the           inverted-index postings [(doc, tf)]
+    GET /search?q=european+parliament&mode=and&k=10&scoring=tf
+                                     ranked multi-term search over the
+                                     index: documents holding every term
+                                     (mode=and) or any (mode=or), best
+                                     score first (tf or tfidf)
 """
 
 from __future__ import annotations
@@ -73,6 +78,19 @@ def make_app(wordcount=None, index=None):
         return {"word": word,
                 "postings": [{"doc": d, "tf": t}
                              for d, t in res.lookup(word)]}
+
+    @app.get("/search")
+    def search(q: str, mode: str = "and", k: int = 10, scoring: str = "tf"):
+        res = _ix()
+        terms = res._terms(q)
+        try:
+            out = res.search(terms, mode=mode, k=k, scoring=scoring)
+        except ValueError as e:  # k, term count, mode or scoring off limits
+            raise HTTPException(422, str(e))
+        return {"query": q,
+                "terms": [t.decode("utf-8", "replace") for t in terms],
+                "hits": out.hits,
+                "results": [{"doc": d, "score": sc} for d, sc in out.docs]}
 
     return app
 

@@ -349,8 +349,10 @@ class Server:
                 for k, v in mine:
                     ks, vs = self.fns.mapfn_gpu_pairs(k, v)
                     kcols.append(torch.as_tensor(ks, dtype=torch.int64))
+                    # floats stage as f64 from the start: as_tensor's
+                    # default (f32) would round them before the widening
                     vt = torch.as_tensor(vs)
-                    vcols.append(vt.to(torch.float64)
+                    vcols.append(torch.as_tensor(vs, dtype=torch.float64)
                                  if vt.is_floating_point()
                                  else vt.to(torch.int64))
                 if kcols:
