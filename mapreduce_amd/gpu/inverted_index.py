@@ -15,6 +15,10 @@ Pipeline per rank (GPU):
     stable by wordhash -> doc lists ordered within each word
   [world > 1] exchange by wordhash partition (mulhi), re-sort, re-merge
   segment by wordhash -> doc-list offsets per word + exemplar bytes
+  [positions=True, single rank] the occurrence stream is kept as well:
+    token_ordinals -> (doc, ordinal within doc) per occurrence; sorted by
+    (doc, ord) then stable by wordhash it lies in posting order, so the
+    positions of posting j are the slice pos_offsets[j] + [0, tf[j])
 (CPU tier keeps the sort-first reference shape.)
 """
 
@@ -47,6 +51,11 @@ class InvertedIndexResult:
                                    # (ops/_cpu.py tokenize_words)
     ndocs: Optional[int] = None  # documents indexed (the N of tf-idf);
                                  # None when the job ran on several ranks
+    # positional layer (InvertedIndexJob(..., positions=True)), else None:
+    # posting j owns positions[pos_offsets[j]:pos_offsets[j + 1]], the
+    # ascending 0-based token ordinals of the word within the document
+    positions: Optional[torch.Tensor] = None    # i32[occurrences]
+    pos_offsets: Optional[torch.Tensor] = None  # i64[postings + 1]
 
     def to_host(self):
         lens, blob = ops.extract_words(self.blob_src, self.pos)
@@ -248,6 +257,73 @@ class InvertedIndexResult:
         return self.search_batch([terms], mode=mode, k=k, scoring=scoring,
                                  ndocs=ndocs)[0]
 
+    @staticmethod
+    def _phrase_terms(query) -> list:
+        """A phrase as its ordered byte-string terms: split like _terms,
+        but duplicates stay ("a a b" is three terms)."""
+        if isinstance(query, (str, bytes)):
+            query = query.split()
+        return [bytes(t.encode() if isinstance(t, str) else t)
+                for t in query]
+
+    def _need_positions(self) -> None:
+        if self.positions is None or self.pos_offsets is None:
+            raise ValueError(
+                "this index has no positional layer; build it with "
+                "InvertedIndexJob(..., positions=True)")
+
+    def phrase_batch(self, queries, k: int = 10) -> List[SearchResult]:
+        """Exact-phrase search of many queries at once: one
+        ops.postings_phrase call, two uploads (term hashes, offsets) and
+        one readback whatever the number of queries.  See phrase()."""
+        self._need_positions()
+        hashes, offs = [], [0]
+        for query in queries:
+            hashes.extend(self._term_hash(t)
+                          for t in self._phrase_terms(query))
+            offs.append(len(hashes))
+        d, s, n, h = ops.postings_phrase(
+            self.keys, self.doc_offsets, self.docs, self.tf,
+            self.pos_offsets, self.positions,
+            torch.tensor(hashes, dtype=torch.int64),
+            torch.tensor(offs, dtype=torch.int64), k)
+        k = d.shape[1]
+        host = torch.cat([d, s, n[:, None], h[:, None]], dim=1).cpu().tolist()
+        return [SearchResult(row[2 * k + 1],
+                             list(zip(row[:row[2 * k]],
+                                      row[k:k + row[2 * k]])))
+                for row in host]
+
+    def phrase(self, terms, k: int = 10) -> SearchResult:
+        """Documents holding the terms next to each other, in this order.
+
+        terms: a str/bytes split on whitespace, or a sequence of terms;
+        repeated terms count ("a a" needs two consecutive a).  Words are
+        adjacent when their token ordinals are, whatever whitespace lies
+        between them.  score = how often the phrase occurs in the document;
+        equal scores order by ascending doc id.  -> SearchResult(hits,
+        [(doc, score), ...]) with at most k documents.  Needs an index
+        built with positions=True (ValueError otherwise)."""
+        return self.phrase_batch([terms], k=k)[0]
+
+    def lookup_positions(self, word) -> list:
+        """One word's positional postings [(doc, [ord, ...]), ...]: the
+        token ordinals of every occurrence, ascending, per document."""
+        self._need_positions()
+        ki = self._term_hash(word)
+        sk = self._signed_keys()
+        q = torch.tensor([ki ^ (-1 << 63)], dtype=torch.int64,
+                         device=sk.device)
+        i = int(torch.searchsorted(sk, q).item())
+        if i >= self.keys.numel() or int(self.keys[i].item()) != ki:
+            return []
+        o0, o1 = self.doc_offsets[i:i + 2].cpu().tolist()
+        po = self.pos_offsets[o0:o1 + 1].cpu().tolist()
+        docs = self.docs[o0:o1].cpu().tolist()
+        flat = self.positions[po[0]:po[-1]].cpu().tolist()
+        return [(d, flat[a - po[0]:b - po[0]])
+                for d, a, b in zip(docs, po[:-1], po[1:])]
+
 
 _SM64_C0 = 0x9E3779B97F4A7C15 - (1 << 64)
 _SM64_C1 = 0xBF58476D1CE4E5B9 - (1 << 64)
@@ -269,11 +345,41 @@ def splitmix64_t(x: torch.Tensor) -> torch.Tensor:
 
 
 class InvertedIndexJob:
-    def __init__(self, device, group=None, doc_base: int = 0):
+    def __init__(self, device, group=None, doc_base: int = 0,
+                 positions: bool = False):
         self.device = torch.device(device)
         self.group = group
         self.rank, self.world = dx.world_info(group)
         self.doc_base = doc_base  # global id of this rank's first doc
+        # also keep every occurrence's token ordinal (phrase search);
+        # single rank only
+        self.positions = bool(positions)
+
+    def _positional_layer(self, text, starts, k2, p, tf, doc_bits: int):
+        """GPU: the occurrence stream (composite key, pos) without pads ->
+        (positions i32[nocc], pos_offsets i64[np + 1]) in posting order.
+        Occurrences are sorted by (doc, ord) over the bits that exist, then
+        stably by wordhash — the order of the postings, whose tf are the
+        slice lengths."""
+        doc, ordn = ops.token_ordinals(text, p, starts)
+        doc = doc + self.doc_base
+        wh = k2 ^ splitmix64_t(doc)
+        comp = (doc << 32) | ordn.to(torch.int64)
+        comp, wh = ops.sort_by_key(comp, wh, bits=32 + doc_bits)
+        wh, comp = ops.sort_by_key(wh, comp, bits=64)
+        return self._finish_positions(
+            (comp & 0xFFFFFFFF).to(torch.int32), tf)
+
+    @staticmethod
+    def _finish_positions(positions, tf):
+        pos_offsets = torch.zeros(tf.numel() + 1, dtype=torch.int64,
+                                  device=tf.device)
+        torch.cumsum(tf, 0, out=pos_offsets[1:])
+        total = int(pos_offsets[-1].item())
+        assert total == positions.numel(), (
+            f"positional layer: {positions.numel()} occurrences for "
+            f"term frequencies summing to {total}")
+        return positions, pos_offsets
 
     def _sort_by_doc_then_hash(self, h, d, p, max_doc: int = 1 << 30):
         # LSD composite: stable sorts, least-significant key first; doc
@@ -323,6 +429,22 @@ class InvertedIndexJob:
             splits: Optional[List[Tuple[int, int]]] = None
             ) -> InvertedIndexResult:
         dev = self.device
+        if self.positions:
+            import os
+            if self.world > 1 or dx.force_collectives():
+                raise NotImplementedError(
+                    "positions=True builds a single-rank index: the "
+                    "exchange carries (word, doc, tf), not occurrences")
+            if dev.type == "cuda" and \
+                    os.environ.get("MR_II_CACHE", "0") == "1":
+                raise ValueError(
+                    "MR_II_CACHE=1 absorbs occurrences into the LDS cache; "
+                    "positions=True needs every occurrence")
+            if text.numel() >= 2 ** 31:
+                raise ValueError(
+                    f"positions=True: text of {text.numel()} bytes; "
+                    "token ordinals are 32-bit")
+        positions = pos_offsets = None
         if splits is None:
             splits = [(0, int(text.numel()))]
         starts = torch.tensor([s for s, _ in splits] + [splits[-1][1]],
@@ -398,6 +520,10 @@ class InvertedIndexJob:
             d1, h1, tf1, p1 = ops.sort_by_key(ud, uh, tf, upos,
                                               bits=doc_bits)
             uh, ud, tf, up = ops.sort_by_key(h1, d1, tf1, p1, bits=64)
+            if self.positions:
+                real = k2 != -1  # HT_EMPTY chunk padding of the spill
+                positions, pos_offsets = self._positional_layer(
+                    text, starts, k2[real], p[real], tf, doc_bits)
         else:
             h, p, n = ops.tokenize_words(text)
             byte_off = p >> 16
@@ -405,6 +531,11 @@ class InvertedIndexJob:
             d = d + self.doc_base
             h, d, p = self._sort_by_doc_then_hash(h, d, p, max_doc)
             uh, ud, tf, up = self._segment_pairs(h, d, p)
+            if self.positions:
+                # the tokenizer emits in text order and both sorts are
+                # stable: occurrences already lie in (word, doc, ord) order
+                _, ordn = ops.token_ordinals(text, p, starts)
+                positions, pos_offsets = self._finish_positions(ordn, tf)
 
         blob_src = text
         if self.world > 1 or dx.force_collectives():
@@ -518,4 +649,5 @@ class InvertedIndexJob:
             keys=wk, doc_offsets=offsets, docs=ud, tf=tf, pos=wpos,
             blob_src=blob_src,
             hash_kind="wordhash64" if dev.type == "cuda" else "fnv1a64",
-            ndocs=self.doc_base + len(splits) if self.world == 1 else None)
+            ndocs=self.doc_base + len(splits) if self.world == 1 else None,
+            positions=positions, pos_offsets=pos_offsets)

@@ -528,3 +528,91 @@ def postings_search(keys: torch.Tensor, doc_offsets: torch.Tensor,
         tf.contiguous(), weights.contiguous(),
         qkeys.to(dev).contiguous(), qoff.to(dev).contiguous(), k,
         _POSTINGS_MODES[mode]))
+
+
+# ---------------------------------------------------------------------------
+# positional index: token ordinals and exact-phrase search
+# ---------------------------------------------------------------------------
+
+TOKEN_ORDINALS_GRANULE = 64  # text bytes per counted granule (HIP kernel)
+
+
+def token_ordinals_caps():
+    """-> (GRANULE,): the extension's own value on a GPU machine, the
+    Python constant above on the CPU tier."""
+    if torch.cuda.is_available():
+        return tuple(int(c) for c in ext().token_ordinals_caps())
+    return (TOKEN_ORDINALS_GRANULE,)
+
+
+def token_ordinals(text: torch.Tensor, pos: torch.Tensor,
+                   starts: torch.Tensor):
+    """Document and 0-based token ordinal of each word occurrence.
+
+    text u8; pos i64[n], the tokenizer's off << 16 | len of each
+    occurrence; starts i64[ndocs + 1], the documents' byte offsets plus
+    the end.  doc = searchsorted(starts, off, right) - 1 (the build's own
+    rule); ord = the number of word starts in [starts[doc], off), a word
+    start being a non-whitespace byte at offset 0 or after a whitespace
+    byte, so a split that begins mid-word holds no start for the fragment.
+    -> (doc i64[n], ord i32[n]).  Texts below 2^31 bytes; the occurrences
+    need no order; no host sync."""
+    if text.numel() >= 2 ** 31:
+        raise ValueError(
+            f"token_ordinals: text of {text.numel()} bytes; ordinals are "
+            "32-bit")
+    if starts.numel() < 1:
+        raise ValueError("starts holds ndocs + 1 offsets")
+    if not text.is_cuda:
+        from . import _cpu
+        return _cpu.token_ordinals(text, pos, starts)
+    return tuple(ext().token_ordinals(text.contiguous(), pos.contiguous(),
+                                      starts.contiguous()))
+
+
+def postings_phrase(keys: torch.Tensor, doc_offsets: torch.Tensor,
+                    docs: torch.Tensor, tf: torch.Tensor,
+                    pos_offsets: torch.Tensor, positions: torch.Tensor,
+                    qkeys: torch.Tensor, qoff: torch.Tensor, k: int):
+    """Exact-phrase search of a batch of queries over the positional index:
+    the CSR arrays of postings_search plus pos_offsets i64[np + 1] into
+    positions i32[nocc], posting j owning the ascending token ordinals
+    positions[pos_offsets[j] : pos_offsets[j] + tf[j]].  Query q is the
+    ORDERED term hashes qkeys[qoff[q]:qoff[q+1]], duplicates kept.
+
+    A document matches iff every term has a posting for it and some s >= 0
+    has s + i among term i's positions for every i; score = the number of
+    such s (tf for one term).  No terms or an unknown term: no matches.
+    Order: score descending, doc ascending on equal score.
+
+    -> (docs i64[nq, k], scores i64[nq, k], n i64[nq] = min(k, hits),
+    hits i64[nq]); unused slots hold doc = -1, score = 0.  Checks, caps
+    and uploads are those of postings_search."""
+    tmax, kmax, _ = postings_search_caps()
+    k = int(k)
+    if not 1 <= k <= kmax:
+        raise ValueError(f"k must be in [1, {kmax}], got {k}")
+    if qoff.numel() < 1:
+        raise ValueError("qoff holds nq + 1 offsets")
+    if pos_offsets.numel() != docs.numel() + 1:
+        raise ValueError("pos_offsets holds one offset per posting + 1")
+    if positions.dtype != torch.int32:
+        raise ValueError("positions must be int32")
+    qo = qoff.cpu()
+    if qo.numel() > 1:
+        per = qo[1:] - qo[:-1]
+        if int(per.min()) < 0 or int(qo[0]) < 0 \
+                or int(qo[-1]) > qkeys.numel():
+            raise ValueError("qoff must ascend within qkeys")
+        if int(per.max()) > tmax:
+            raise ValueError(
+                f"at most {tmax} terms per query, got {int(per.max())}")
+    dev = keys.device
+    if not keys.is_cuda:
+        from . import _cpu
+        return _cpu.postings_phrase(keys, doc_offsets, docs, tf, pos_offsets,
+                                    positions, qkeys.cpu(), qo, k)
+    return tuple(ext().postings_phrase(
+        keys.contiguous(), doc_offsets.contiguous(), docs.contiguous(),
+        tf.contiguous(), pos_offsets.contiguous(), positions.contiguous(),
+        qkeys.to(dev).contiguous(), qoff.to(dev).contiguous(), k))

@@ -229,3 +229,96 @@ def postings_search(keys, doc_offsets, docs, tf, weights, qkeys, qoff,
         out_scores[q, :n] = score[order[:n]]
     return (torch.from_numpy(out_docs), torch.from_numpy(out_scores),
             torch.from_numpy(out_n), torch.from_numpy(out_hits))
+
+
+def token_ordinals(text: torch.Tensor, pos: torch.Tensor,
+                   starts: torch.Tensor):
+    """NumPy form of the token_ordinals kernels (same outputs): per
+    occurrence pos = off << 16 | len, doc = index of the last starts[]
+    entry <= off (-1 if none) and ord = word starts in [starts[doc], off),
+    a word start being a non-whitespace byte at offset 0 or after a
+    whitespace byte.  -> (doc i64[n], ord i32[n])."""
+    data = np.frombuffer(bytes(text.contiguous().numpy().tobytes()),
+                         dtype=np.uint8)
+    n = len(data)
+    ws = (data == 32) | ((data >= 9) & (data <= 13))
+    prev_ws = np.ones(n, dtype=bool)
+    prev_ws[1:] = ws[:-1]
+    before = np.zeros(n + 1, dtype=np.int64)  # before[x] = starts at < x
+    np.cumsum(~ws & prev_ws, out=before[1:])
+    off = (_u64(pos.contiguous()) >> np.uint64(16)).astype(np.int64)
+    sn = starts.contiguous().numpy()
+    doc = np.searchsorted(sn, off, side="right") - 1
+    at = np.clip(sn[np.maximum(doc, 0)], 0, n)
+    ordn = before[np.clip(off, 0, n)] - before[at]
+    return (torch.from_numpy(doc.astype(np.int64)),
+            torch.from_numpy(ordn.astype(np.int32)))
+
+
+def postings_phrase(keys, doc_offsets, docs, tf, pos_offsets, positions,
+                    qkeys, qoff, k: int):
+    """NumPy form of the postings_phrase kernel (same outputs, bit for
+    bit): per query of ordered terms h_0..h_{T-1} (duplicates kept), the
+    documents holding every term with some s >= 0 such that s + i is a
+    position of h_i for all i; score = the number of such s; best k by
+    score descending then doc ascending."""
+    ku = _u64(keys.contiguous())
+    offs = doc_offsets.contiguous().numpy()
+    dn = docs.contiguous().numpy()
+    tn = tf.contiguous().numpy()
+    po = pos_offsets.contiguous().numpy()
+    pn = positions.contiguous().numpy().astype(np.int64)
+    qk = _u64(qkeys.contiguous())
+    qo = qoff.contiguous().numpy()
+    nq = len(qo) - 1
+    out_docs = np.full((nq, k), -1, dtype=np.int64)
+    out_scores = np.zeros((nq, k), dtype=np.int64)
+    out_n = np.zeros(nq, dtype=np.int64)
+    out_hits = np.zeros(nq, dtype=np.int64)
+    for q in range(nq):
+        rows = []  # per term (first posting, end posting); unknown = empty
+        for h in qk[qo[q]:qo[q + 1]]:
+            r = int(np.searchsorted(ku, h))
+            if r < len(ku) and ku[r] == h:
+                rows.append((int(offs[r]), int(offs[r + 1])))
+            else:
+                rows.append((0, 0))
+        if not rows:
+            continue
+        lens = [b - a for a, b in rows]
+        drv = lens.index(min(lens))
+        cand = dn[rows[drv][0]:rows[drv][1]]
+        keep = np.ones(len(cand), dtype=bool)
+        where = []  # per term: posting index of each candidate doc
+        for a, b in rows:
+            d = dn[a:b]
+            if len(d) == 0:
+                keep[:] = False
+                where.append(np.zeros(len(cand), dtype=np.int64))
+                continue
+            p = np.minimum(np.searchsorted(d, cand), len(d) - 1)
+            keep &= d[p] == cand
+            where.append(a + p)
+        found, score = [], []
+        for c in np.flatnonzero(keep):
+            j = int(where[drv][c])
+            s = pn[po[j]:po[j] + tn[j]] - drv
+            s = s[s >= 0]
+            for i, w in enumerate(where):
+                if i == drv or len(s) == 0:
+                    continue
+                j = int(w[c])
+                s = s[np.isin(s + i, pn[po[j]:po[j] + tn[j]])]
+            if len(s):
+                found.append(cand[c])
+                score.append(len(s))
+        found = np.array(found, dtype=np.int64)
+        score = np.array(score, dtype=np.int64)
+        order = np.lexsort((found, ~score))
+        n = min(k, len(found))
+        out_hits[q] = len(found)
+        out_n[q] = n
+        out_docs[q, :n] = found[order[:n]]
+        out_scores[q, :n] = score[order[:n]]
+    return (torch.from_numpy(out_docs), torch.from_numpy(out_scores),
+            torch.from_numpy(out_n), torch.from_numpy(out_hits))

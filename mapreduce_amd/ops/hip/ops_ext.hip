@@ -17,8 +17,10 @@
 #include "gradsum.hip"
 #include "lex_order.hip"
 #include "mr_kernels.hip"
+#include "postings_phrase.hip"
 #include "postings_query.hip"
 #include "radix_sort.hip"
+#include "token_ordinals.hip"
 
 namespace {
 
@@ -1185,6 +1187,100 @@ std::vector<torch::Tensor> postings_search(
   return {out_docs, out_scores, out_n, out_hits};
 }
 
+// ------------------------------------------------ positional index / phrases
+// caps of token_ordinals: (bytes per counted granule)
+std::vector<long> token_ordinals_caps() { return {TORD_GRANULE}; }
+
+// Per occurrence pos = off << 16 | len: (doc i64[m], ord i32[m]), doc the
+// index of the last starts[] entry <= off (-1 if none) and ord the 0-based
+// token ordinal of the word within that document.  One streaming pass over
+// the text counts word starts per granule, a scan turns the counts into
+// prefixes, one thread per occurrence resolves.  No host sync.
+std::vector<torch::Tensor> token_ordinals(torch::Tensor text,
+                                          torch::Tensor pos,
+                                          torch::Tensor starts) {
+  check_text_u8(text);
+  check_dev_i64(pos, "pos");
+  check_dev_i64(starts, "starts");
+  long n = text.numel();
+  long m = pos.numel();
+  long nstarts = starts.numel();
+  TORCH_CHECK(n < (1L << 31), "token_ordinals: text of ", n,
+              " bytes; ordinals are 32-bit");
+  TORCH_CHECK(nstarts >= 1 && nstarts < (1L << 31),
+              "starts holds ndocs + 1 offsets");
+  auto i32 = torch::TensorOptions().device(text.device()).dtype(torch::kInt32);
+  long ngran = (n + TORD_GRANULE - 1) / TORD_GRANULE;
+  auto prefix = torch::zeros({ngran + 1}, i32);
+  if (ngran) {
+    auto gcount = torch::empty({ngran}, i32);
+    hipLaunchKernelGGL(tord_count_kernel, dim3(grid_for(ngran * 8)),
+                       dim3(TORD_BLOCK), 0, cur_stream(),
+                       text.data_ptr<u8>(), n, gcount.data_ptr<int>(), ngran);
+    prefix.slice(0, 1).copy_(gcount.cumsum(0, torch::kInt32));
+  }
+  auto doc_sb = torch::empty({nstarts}, i32);
+  hipLaunchKernelGGL(tord_before_kernel, dim3(grid_for(nstarts)),
+                     dim3(TORD_BLOCK), 0, cur_stream(), text.data_ptr<u8>(), n,
+                     prefix.data_ptr<int>(), starts.data_ptr<i64>(), nstarts,
+                     doc_sb.data_ptr<int>());
+  auto out_doc = torch::empty({m}, pos.options());
+  auto out_ord = torch::empty({m}, i32);
+  if (m)
+    hipLaunchKernelGGL(tord_resolve_kernel, dim3(grid_for(m)),
+                       dim3(TORD_BLOCK), 0, cur_stream(), text.data_ptr<u8>(),
+                       n, prefix.data_ptr<int>(), u64cp(pos), m,
+                       starts.data_ptr<i64>(), (int)nstarts,
+                       doc_sb.data_ptr<int>(), out_doc.data_ptr<i64>(),
+                       out_ord.data_ptr<int>());
+  return {out_doc, out_ord};
+}
+
+// Exact-phrase twin of postings_search: ordered terms, score = phrase
+// frequency.  pos_offsets i64[np + 1] into positions i32[nocc].
+std::vector<torch::Tensor> postings_phrase(
+    torch::Tensor keys, torch::Tensor doc_offsets, torch::Tensor docs,
+    torch::Tensor tf, torch::Tensor pos_offsets, torch::Tensor positions,
+    torch::Tensor qkeys, torch::Tensor qoff, long k) {
+  check_dev_i64(keys, "keys");
+  check_dev_i64(doc_offsets, "doc_offsets");
+  check_dev_i64(docs, "docs");
+  check_dev_i64(tf, "tf");
+  check_dev_i64(pos_offsets, "pos_offsets");
+  check_dev_i64(qkeys, "qkeys");
+  check_dev_i64(qoff, "qoff");
+  TORCH_CHECK(positions.is_cuda() &&
+                  positions.scalar_type() == torch::kInt32 &&
+                  positions.is_contiguous(),
+              "positions must be contiguous int32 on GPU");
+  long nwords = keys.numel();
+  long np = docs.numel();
+  TORCH_CHECK(doc_offsets.numel() == nwords + 1,
+              "doc_offsets holds nwords + 1 offsets");
+  TORCH_CHECK(tf.numel() == np, "tf must have one entry per doc");
+  TORCH_CHECK(pos_offsets.numel() == np + 1,
+              "pos_offsets holds one offset per posting + 1");
+  TORCH_CHECK(qoff.numel() >= 1, "qoff holds nq + 1 offsets");
+  TORCH_CHECK(k >= 1 && k <= PQ_KMAX, "k must be in [1, ", PQ_KMAX, "]");
+  long nq = qoff.numel() - 1;
+  auto opts = keys.options();
+  auto out_docs = torch::empty({nq, k}, opts);
+  auto out_scores = torch::empty({nq, k}, opts);
+  auto out_n = torch::empty({nq}, opts);
+  auto out_hits = torch::empty({nq}, opts);
+  if (nq)
+    hipLaunchKernelGGL(postings_phrase_kernel, dim3(nq), dim3(PQ_BLOCK), 0,
+                       cur_stream(), u64cp(keys), nwords,
+                       doc_offsets.data_ptr<i64>(), docs.data_ptr<i64>(),
+                       tf.data_ptr<i64>(), np, pos_offsets.data_ptr<i64>(),
+                       positions.data_ptr<int>(), positions.numel(),
+                       u64cp(qkeys), qkeys.numel(), qoff.data_ptr<i64>(),
+                       (int)k, out_docs.data_ptr<i64>(),
+                       out_scores.data_ptr<i64>(), out_n.data_ptr<i64>(),
+                       out_hits.data_ptr<i64>());
+  return {out_docs, out_scores, out_n, out_hits};
+}
+
 // Occupancy of the default word-count tokenizer instantiation on the
 // current device, as the runtime sees it (blocks/CU clips the grid; the
 // register count and static LDS are what decide it).
@@ -1208,6 +1304,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "ranked AND/OR top-k over the inverted index, one block per query");
   m.def("postings_search_caps", &postings_search_caps,
         "(TMAX, KMAX, BUF) of postings_search");
+  m.def("postings_phrase", &postings_phrase,
+        "exact-phrase top-k over the positional index, one block per query");
+  m.def("token_ordinals", &token_ordinals,
+        "(doc, token ordinal within doc) of each occurrence");
+  m.def("token_ordinals_caps", &token_ordinals_caps,
+        "(GRANULE) of token_ordinals");
   m.def("lex_chunk_keys", &lex_chunk_keys,
         "big-endian 8-byte chunk d of each string as a sortable u64");
   m.def("lex_refine", &lex_refine,

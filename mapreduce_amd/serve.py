@@ -23,6 +23,11 @@ Endpoints:
                                      index: documents holding every term
                                      (mode=and) or any (mode=or), best
                                      score first (tf or tfidf)
+    GET /phrase?q=european+parliament&k=10
+                                     exact phrase: documents holding the
+                                     terms next to each other in this
+                                     order, most occurrences first (needs
+                                     an index built with positions=True)
 """
 
 from __future__ import annotations
@@ -92,6 +97,19 @@ def make_app(wordcount=None, index=None):
                 "hits": out.hits,
                 "results": [{"doc": d, "score": sc} for d, sc in out.docs]}
 
+    @app.get("/phrase")
+    def phrase(q: str, k: int = 10):
+        res = _ix()
+        terms = res._phrase_terms(q)
+        try:
+            out = res.phrase(terms, k=k)
+        except ValueError as e:  # k or term count off limits, no positions
+            raise HTTPException(422, str(e))
+        return {"query": q,
+                "terms": [t.decode("utf-8", "replace") for t in terms],
+                "hits": out.hits,
+                "results": [{"doc": d, "score": sc} for d, sc in out.docs]}
+
     return app
 
 
@@ -103,9 +121,10 @@ def serve(wordcount=None, index=None, host: str = "127.0.0.1",
     uvicorn.run(app or make_app(wordcount, index), host=host, port=port)
 
 
-def build_results_from_files(paths, device=None):
+def build_results_from_files(paths, device=None, positions=False):
     """Run wordcount + inverted index over files and return the two
-    result objects (the CLI's one-stop build; GPU if available)."""
+    result objects (the CLI's one-stop build; GPU if available).
+    positions=True adds the index's positional layer (/phrase)."""
     import torch
 
     from .gpu.input import load_corpus
@@ -116,7 +135,7 @@ def build_results_from_files(paths, device=None):
     corpus = load_corpus(list(paths), dev)
     splits = corpus.splits()
     wc = WordCountJob(dev, vocab_estimate=1 << 17).run(corpus.text, splits)
-    ix = InvertedIndexJob(dev).run(corpus.text, splits)
+    ix = InvertedIndexJob(dev, positions=positions).run(corpus.text, splits)
     return wc, ix
 
 
@@ -132,8 +151,11 @@ def main(argv: Optional[list] = None) -> int:
     p.add_argument("--host", default="127.0.0.1")
     p.add_argument("--port", type=int, default=8000)
     p.add_argument("--device", default=None)
+    p.add_argument("--positions", action="store_true",
+                   help="index token positions too (enables /phrase)")
     args = p.parse_args(argv)
-    wc, ix = build_results_from_files(args.files, args.device)
+    wc, ix = build_results_from_files(args.files, args.device,
+                                      positions=args.positions)
     print(f"# serving {wc.nwords or '?'} words, "
           f"{wc.keys.numel()} unique, {len(args.files)} docs "
           f"on {args.host}:{args.port}")
