@@ -150,7 +150,16 @@ _SMALL_SORT_N = 1 << 20  # below this, one stable torch.sort dispatch
 
 def sort_pairs(keys: torch.Tensor, vals: Optional[torch.Tensor] = None,
                bits: int = 64):
-    """Stable LSD radix sort of u64 keys (bit-pattern order) w/ payload."""
+    """Stable sort of u64 keys (bit-pattern order) w/ payload.
+
+    Contract: every key is below 2**bits.  Then the result is the full
+    64-bit stable sort (np.argsort(kind="stable") of the u64 view) on
+    every path, and the inputs are never written.  `bits` only lets the
+    radix sort skip passes that cannot reorder such keys; it is not a
+    mask.  For keys with bits set at or above `bits` the paths differ and
+    the result is unspecified: the in-tree radix sort (and sort_idx32)
+    orders by the low 8 * ceil(bits / 8) bits alone, while the torch path
+    below the small-sort threshold and the CPU tier order by all 64."""
     if not keys.is_cuda:
         from . import _cpu
         return _cpu.sort_pairs(keys, vals, bits)

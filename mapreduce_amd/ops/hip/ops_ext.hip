@@ -597,13 +597,29 @@ void bucket_count(torch::Tensor hashes, torch::Tensor pos,
                   torch::Tensor tkeys, torch::Tensor tvals,
                   torch::Tensor texm, long region_stride, long slots_arg) {
   check_dev_i64(hashes, "hashes");
+  check_dev_i64(pos, "pos");
+  check_dev_i64(bucket_off, "bucket_off");
+  check_dev_i64(tkeys, "tkeys");
+  check_dev_i64(tvals, "tvals");
+  if (texm.numel()) check_dev_i64(texm, "texm");
+  TORCH_CHECK(pos.numel() >= hashes.numel(),
+              "pos must hold one entry per hash");
+  TORCH_CHECK(nbuckets >= 1 && slices >= 1, "nbuckets and slices >= 1");
+  TORCH_CHECK(nbuckets * slices < (1L << 31), "nbuckets * slices too large");
   long cap = tkeys.numel();
-  TORCH_CHECK((cap & (cap - 1)) == 0, "table capacity must be a power of 2");
+  TORCH_CHECK(cap > 0 && (cap & (cap - 1)) == 0,
+              "table capacity must be a power of 2");
+  TORCH_CHECK(tvals.numel() == cap &&
+                  (texm.numel() == 0 || texm.numel() == cap),
+              "tvals (and texm, when tracked) must match tkeys");
   // region_stride > 0: bucket_off holds per-bucket LENGTHS and bucket b's
   // data lives at [b*stride, b*stride+len[b]) (bucketed direct spill)
   TORCH_CHECK(bucket_off.numel() >= (region_stride > 0 ? nbuckets
                                                        : nbuckets + 1),
               "bucket_off size");
+  TORCH_CHECK(region_stride <= 0 ||
+                  hashes.numel() >= nbuckets * region_stride,
+              "hashes must hold nbuckets regions of region_stride entries");
   // slots: caller picks (1024 = 8 blocks/CU is now the winner for BOTH
   // wordcount and the inverted index — r2 joint sweep showed slots and
   // slices interact: smaller tables buy occupancy that more slices
@@ -959,11 +975,24 @@ std::vector<torch::Tensor> radix_bucketize(torch::Tensor keys,
   return {kout, vout, bucket_off};
 }
 
+// what this process's sorts run: (records per tile, 1 if the direct-scatter
+// kernel of MR_RADIX_V1=1 is selected else 0) — both are fixed at first use
+std::vector<long> radix_sort_caps() {
+  return {rs_tile(), radix_v1_forced() ? 1L : 0L};
+}
+
 std::vector<torch::Tensor> radix_sort_pairs(torch::Tensor keys,
                                             torch::Tensor vals, int bits) {
   check_dev_i64(keys, "keys");
   long n = keys.numel();
   bool has_vals = vals.numel() > 0;
+  if (has_vals) {
+    TORCH_CHECK(vals.is_cuda() && vals.is_contiguous() && vals.numel() == n,
+                "vals must be contiguous on GPU, one per key");
+    TORCH_CHECK(vals.scalar_type() == torch::kInt64, "vals must be int64");
+    TORCH_CHECK(vals.device() == keys.device(),
+                "vals must be on the keys' device");
+  }
   if (n == 0) return {keys, vals};
   TORCH_CHECK(bits >= 1 && bits <= 64, "bits in [1,64]");
   int passes = (bits + 7) / 8;
@@ -1353,6 +1382,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("pos_len", &pos_len);
   m.def("gather_bytes", &gather_bytes);
   m.def("radix_sort_pairs", &radix_sort_pairs);
+  m.def("radix_sort_caps", &radix_sort_caps,
+        "(tile records, direct scatter 0/1) of this process's radix sorts");
   m.def("radix_pass", &radix_pass);
   m.def("radix_bucketize", &radix_bucketize, py::arg("keys"),
         py::arg("vals"), py::arg("shift"), py::arg("skip_empty") = false,

@@ -109,8 +109,23 @@ def test_hash_table_big_capacity_chunked_extract(dev):
     assert np.array_equal(sk.cpu().numpy().view(np.uint64), exp)
 
 
-@pytest.mark.parametrize("n", [0, 1, 63, 64, 2048, 2049, 1_000_000])
+def _small_sort_n():
+    import os
+    from mapreduce_amd import ops
+    return int(os.environ.get("MR_SMALL_SORT_N", ops._SMALL_SORT_N))
+
+
+def _empty(dev):
+    return torch.empty(0, dtype=torch.int64, device=dev)
+
+
+@pytest.mark.parametrize("n", [0, 1, 63, 64, 2048, 2049, 1_000_000,
+                               (1 << 20) + 1])
 def test_radix_sort_keys(dev, n):
+    """First half: ops.sort_by_key, which below the small-sort threshold
+    (2^20 keys; every size here but the last) is one stable torch.sort
+    (rocPRIM) and from it up the in-tree radix sort.  Second half: the same
+    input through radix_sort_pairs itself, whatever the size."""
     from mapreduce_amd import ops
     rng = np.random.default_rng(n + 1)
     keys_np = rng.integers(0, 2 ** 63 - 1, size=n, dtype=np.uint64)
@@ -119,12 +134,20 @@ def test_radix_sort_keys(dev, n):
     (sk,) = ops.sort_by_key(keys)
     got = u64view(sk.cpu())
     assert np.array_equal(got, np.sort(keys_np))
+    rk, _ = ops.ext().radix_sort_pairs(keys, _empty(dev), 64)
+    assert np.array_equal(u64view(rk.cpu()), np.sort(keys_np))
+    assert np.array_equal(u64view(keys.cpu()), keys_np)  # input untouched
 
 
 def test_radix_sort_pairs_stable(dev):
+    """Above the small-sort threshold, so ops.sort_pairs runs the in-tree
+    radix sort (first half); the second half calls radix_sort_pairs and
+    radix_sort_idx32 directly.  The torch path of the wrapper is compared
+    with the same oracle in test_radix_full_sort.py."""
     from mapreduce_amd import ops
     rng = np.random.default_rng(3)
-    n = 300_000
+    n = (1 << 20) + 4099
+    assert n >= _small_sort_n()
     keys_np = rng.integers(0, 64, size=n, dtype=np.uint64)  # heavy dupes
     vals_np = np.arange(n, dtype=np.uint64)
     keys = torch.from_numpy(keys_np.view(np.int64)).to(dev)
@@ -135,15 +158,31 @@ def test_radix_sort_pairs_stable(dev):
     order = np.argsort(keys_np, kind="stable")
     assert np.array_equal(got_k, keys_np[order])
     assert np.array_equal(got_v, vals_np[order])  # stability
+    rk, rv = ops.ext().radix_sort_pairs(keys, vals, 64)
+    assert np.array_equal(u64view(rk.cpu()), keys_np[order])
+    assert np.array_equal(u64view(rv.cpu()), vals_np[order])
+    ik, perm = ops.ext().radix_sort_idx32(keys, 64)
+    assert np.array_equal(u64view(ik.cpu()), keys_np[order])
+    assert np.array_equal(perm.cpu().numpy().astype(np.int64), order)
+    assert np.array_equal(u64view(keys.cpu()), keys_np)  # inputs untouched
+    assert np.array_equal(u64view(vals.cpu()), vals_np)
 
 
 def test_radix_sort_fewer_bits(dev):
+    """bits=16 runs two of the eight passes.  First half: ops.sort_by_key
+    above the small-sort threshold, i.e. the in-tree radix sort; second
+    half: radix_sort_pairs directly.  Keys are below 2**16, where both
+    must equal the full 64-bit sort."""
     from mapreduce_amd import ops
     rng = np.random.default_rng(5)
-    keys_np = rng.integers(0, 2 ** 16, size=100_000, dtype=np.uint64)
+    n = (1 << 20) + 77
+    assert n >= _small_sort_n()
+    keys_np = rng.integers(0, 2 ** 16, size=n, dtype=np.uint64)
     keys = torch.from_numpy(keys_np.view(np.int64)).to(dev)
     (sk,) = ops.sort_by_key(keys, bits=16)
     assert np.array_equal(u64view(sk.cpu()), np.sort(keys_np))
+    rk, _ = ops.ext().radix_sort_pairs(keys, _empty(dev), 16)
+    assert np.array_equal(u64view(rk.cpu()), np.sort(keys_np))
 
 
 def test_reduce_by_key_sorted_i64(dev):
@@ -195,13 +234,18 @@ def test_partition_hist_matches_mulhi(dev):
     n = 500_000
     keys_np = rng.integers(0, 2 ** 64 - 1, size=n, dtype=np.uint64)
     keys = torch.from_numpy(keys_np.view(np.int64)).to(dev)
-    for P in (1, 2, 7, 8, 15, 64):
+    # 1000 and 1024 (= MAX_PARTS) take the strided LDS init and flush loops
+    # of the 256-thread block through four rounds
+    for P in (1, 2, 7, 8, 15, 64, 1000, 1024):
         hist = ops.partition_counts(keys, P).cpu().numpy()
         exp = np.bincount(
             ((keys_np.astype(object) * P) >> 64).astype(np.int64),
             minlength=P)
         assert np.array_equal(hist, exp), P
         assert hist.sum() == n
+        assert hist.size == P and (P < 1000 or hist.min() > 0)
+    with pytest.raises(RuntimeError, match="nparts too large"):
+        ops.partition_counts(keys, 1025)
 
 
 def test_extract_words_roundtrip(dev):
