@@ -625,3 +625,97 @@ def postings_phrase(keys: torch.Tensor, doc_offsets: torch.Tensor,
         keys.contiguous(), doc_offsets.contiguous(), docs.contiguous(),
         tf.contiguous(), pos_offsets.contiguous(), positions.contiguous(),
         qkeys.to(dev).contiguous(), qoff.to(dev).contiguous(), k))
+
+
+# ---------------------------------------------------------------------------
+# equi-join of two key-sorted columns (the join step of the reduce-side join)
+# ---------------------------------------------------------------------------
+
+# caps of the join_expand kernel (ops/hip/join.hip): output rows per tile,
+# offsets staged in LDS per tile.  The CPU tier has no tiles; it reports the
+# same values so tests size their cases alike on both tiers.
+JOIN_TILE = 2048
+JOIN_LDS_ROWS = 1024
+# caps of the windowed bounds kernel: left rows per tile, right keys of a
+# tile's window staged in LDS
+JOIN_BOUNDS_TILE = 1024
+JOIN_BOUNDS_WIN = 2048
+
+_JOIN_HOWS = ("inner", "left", "semi", "anti")
+
+
+class JoinTooLarge(ValueError):
+    """The join would produce more than max_rows output rows."""
+
+    def __init__(self, total: int, max_rows: int):
+        super().__init__(
+            f"join produces {total} rows, over the limit of {max_rows} "
+            "(max_rows)")
+        self.total = int(total)
+        self.max_rows = int(max_rows)
+
+
+def join_caps():
+    """-> (JOIN_TILE, JOIN_LDS_ROWS): the extension's own values on a GPU
+    machine, the Python constants above on the CPU tier."""
+    if torch.cuda.is_available():
+        return tuple(int(c) for c in ext().join_caps())
+    return JOIN_TILE, JOIN_LDS_ROWS
+
+
+def join_bounds_caps():
+    """-> (JOIN_BOUNDS_TILE, JOIN_BOUNDS_WIN), as join_caps."""
+    if torch.cuda.is_available():
+        return tuple(int(c) for c in ext().join_bounds_caps())
+    return JOIN_BOUNDS_TILE, JOIN_BOUNDS_WIN
+
+
+def join_bounds(lkeys: torch.Tensor, rkeys: torch.Tensor):
+    """Pass 1 of join_sorted: (lo i64[nl], cnt i64[nl]), the start and the
+    length of each left key's run of equal right keys.  No host sync, so a
+    caller can size (or refuse) the output before it is expanded.
+    MR_JOIN_BOUNDS_ROW=1 (read per call) runs the thread-per-row kernel
+    instead of the block-window one, for A/B."""
+    if not lkeys.is_cuda and not rkeys.is_cuda:
+        from . import _cpu
+        return _cpu.join_bounds(lkeys, rkeys)
+    import os
+    window = os.environ.get("MR_JOIN_BOUNDS_ROW", "0") != "1"
+    return tuple(ext().join_bounds(lkeys.contiguous(), rkeys.contiguous(),
+                                   window))
+
+
+def join_sorted(lkeys: torch.Tensor, rkeys: torch.Tensor,
+                how: str = "inner", max_rows: Optional[int] = None,
+                bounds=None):
+    """Equi-join of two key columns, each sorted ascending in u64 bit order
+    (i64 tensors holding u64 bit patterns).  Sortedness is the caller's
+    contract and is not checked; the inputs are never written.
+
+    how "inner" / "left": -> (li i64[total], ri i64[total]), row indices
+    into the two inputs, ordered by li then ri; under "left" an unmatched
+    left row appears once, in its place, with ri == -1.
+    how "semi" / "anti": -> li i64[m] ascending, the left rows with / without
+    a match.
+
+    max_rows: raise JoinTooLarge before allocating the output when it would
+    hold more rows.  bounds: the pair join_bounds returned for these
+    columns, when the caller already holds it.  One host sync (the output
+    size); semi and anti sync in torch.nonzero instead."""
+    if how not in _JOIN_HOWS:
+        raise ValueError(f"how must be one of {_JOIN_HOWS}, got {how!r}")
+    if not lkeys.is_cuda and not rkeys.is_cuda:
+        from . import _cpu
+        return _cpu.join_sorted(lkeys, rkeys, how, max_rows, bounds)
+    lo, cnt = bounds if bounds is not None else join_bounds(lkeys, rkeys)
+    if how == "semi":
+        return torch.nonzero(cnt > 0).squeeze(1)
+    if how == "anti":
+        return torch.nonzero(cnt == 0).squeeze(1)
+    per = cnt if how == "inner" else cnt.clamp(min=1)
+    off = torch.zeros(cnt.numel() + 1, dtype=torch.int64, device=cnt.device)
+    torch.cumsum(per, 0, out=off[1:])
+    total = int(off[-1].item())  # the op's only host sync
+    if max_rows is not None and total > max_rows:
+        raise JoinTooLarge(total, max_rows)
+    return tuple(ext().join_expand(off, lo, cnt, total))

@@ -322,3 +322,38 @@ def postings_phrase(keys, doc_offsets, docs, tf, pos_offsets, positions,
         out_scores[q, :n] = score[order[:n]]
     return (torch.from_numpy(out_docs), torch.from_numpy(out_scores),
             torch.from_numpy(out_n), torch.from_numpy(out_hits))
+
+
+def join_bounds(lkeys: torch.Tensor, rkeys: torch.Tensor):
+    """-> (lo i64[nl], cnt i64[nl]): the start and the length of each left
+    key's run of equal right keys, both columns sorted in u64 bit order."""
+    if lkeys.dtype != torch.int64 or rkeys.dtype != torch.int64:
+        raise TypeError("join: key columns must be int64")
+    lk = _u64(lkeys.contiguous())
+    rk = _u64(rkeys.contiguous())
+    lo = np.searchsorted(rk, lk, side="left").astype(np.int64)
+    cnt = np.searchsorted(rk, lk, side="right").astype(np.int64) - lo
+    return torch.from_numpy(lo), torch.from_numpy(cnt)
+
+
+def join_sorted(lkeys: torch.Tensor, rkeys: torch.Tensor, how: str,
+                max_rows: Optional[int] = None, bounds=None):
+    """NumPy form of ops.join_sorted (same outputs, row for row):
+    np.searchsorted gives each left key its run of equal right keys,
+    np.repeat and range arithmetic expand the runs."""
+    lo, cnt = bounds if bounds is not None else join_bounds(lkeys, rkeys)
+    lo, cnt = lo.numpy(), cnt.numpy()
+    if how == "semi":
+        return torch.from_numpy(np.flatnonzero(cnt > 0).astype(np.int64))
+    if how == "anti":
+        return torch.from_numpy(np.flatnonzero(cnt == 0).astype(np.int64))
+    per = cnt if how == "inner" else np.maximum(cnt, 1)
+    total = int(per.sum())
+    if max_rows is not None and total > max_rows:
+        from . import JoinTooLarge
+        raise JoinTooLarge(total, max_rows)
+    li = np.repeat(np.arange(len(cnt), dtype=np.int64), per)
+    off = np.cumsum(per) - per
+    ri = lo[li] + (np.arange(total, dtype=np.int64) - off[li])
+    ri[cnt[li] == 0] = -1
+    return torch.from_numpy(li), torch.from_numpy(ri)

@@ -15,6 +15,7 @@
 #include <utility>
 
 #include "gradsum.hip"
+#include "join.hip"
 #include "lex_order.hip"
 #include "mr_kernels.hip"
 #include "postings_phrase.hip"
@@ -1310,6 +1311,73 @@ std::vector<torch::Tensor> postings_phrase(
   return {out_docs, out_scores, out_n, out_hits};
 }
 
+// ------------------------------------------------------------ sorted equi-join
+// caps of the join kernels: (output rows per tile, off entries in LDS)
+std::vector<long> join_caps() { return {JOIN_TILE, JOIN_LDS_ROWS}; }
+
+// caps of the windowed bounds pass: (left rows per tile, window keys in LDS)
+std::vector<long> join_bounds_caps() { return {JOIN_BTILE, JOIN_WIN}; }
+
+// Pass 1 over two key columns sorted ascending in u64 bit order:
+// (lo i64[nl], cnt i64[nl]), lo[i] the first right index with rk >= lk[i]
+// and cnt[i] the number of right rows equal to lk[i].  window picks the
+// block-window kernel over the thread-per-row one (same outputs).  No host
+// sync.
+std::vector<torch::Tensor> join_bounds(torch::Tensor lkeys,
+                                       torch::Tensor rkeys, bool window) {
+  check_dev_i64(lkeys, "lkeys");
+  check_dev_i64(rkeys, "rkeys");
+  TORCH_CHECK(lkeys.device() == rkeys.device(),
+              "lkeys and rkeys must be on the same device");
+  long nl = lkeys.numel();
+  long nr = rkeys.numel();
+  auto lo = torch::empty({nl}, lkeys.options());
+  auto cnt = torch::empty({nl}, lkeys.options());
+  const u64* rp = nr ? u64cp(rkeys) : nullptr;
+  if (nl && window) {
+    long ntiles = (nl + JOIN_BTILE - 1) / JOIN_BTILE;
+    long blocks = ntiles < kMaxBlocks ? ntiles : kMaxBlocks;
+    hipLaunchKernelGGL(join_bounds_window_kernel, dim3(blocks),
+                       dim3(JOIN_BLOCK), 0, cur_stream(), u64cp(lkeys), nl,
+                       rp, nr, ntiles, lo.data_ptr<i64>(),
+                       cnt.data_ptr<i64>());
+  } else if (nl) {
+    hipLaunchKernelGGL(join_bounds_kernel, dim3(grid_for(nl)),
+                       dim3(JOIN_BLOCK), 0, cur_stream(), u64cp(lkeys), nl,
+                       rp, nr, lo.data_ptr<i64>(), cnt.data_ptr<i64>());
+  }
+  return {lo, cnt};
+}
+
+// Pass 2: off i64[nl + 1] = exclusive cumsum of the per-left-row output
+// counts with off[nl] == total (read back by the caller, who sizes the
+// output with it).  -> (li i64[total], ri i64[total]), ri == -1 on the
+// output row of a left row with cnt == 0.
+std::vector<torch::Tensor> join_expand(torch::Tensor off, torch::Tensor lo,
+                                       torch::Tensor cnt, long total) {
+  check_dev_i64(off, "off");
+  check_dev_i64(lo, "lo");
+  check_dev_i64(cnt, "cnt");
+  TORCH_CHECK(off.device() == lo.device() && off.device() == cnt.device(),
+              "off, lo and cnt must be on the same device");
+  long nl = lo.numel();
+  TORCH_CHECK(cnt.numel() == nl && off.numel() == nl + 1,
+              "off holds one offset per left row + 1, cnt one count per row");
+  TORCH_CHECK(total >= 0 && (total == 0 || nl > 0),
+              "total must be >= 0, and 0 without left rows");
+  auto li = torch::empty({total}, off.options());
+  auto ri = torch::empty({total}, off.options());
+  if (total) {
+    long ntiles = (total + JOIN_TILE - 1) / JOIN_TILE;
+    long blocks = ntiles < kMaxBlocks ? ntiles : kMaxBlocks;
+    hipLaunchKernelGGL(join_expand_kernel, dim3(blocks), dim3(JOIN_BLOCK), 0,
+                       cur_stream(), off.data_ptr<i64>(), nl,
+                       lo.data_ptr<i64>(), cnt.data_ptr<i64>(), total, ntiles,
+                       li.data_ptr<i64>(), ri.data_ptr<i64>());
+  }
+  return {li, ri};
+}
+
 // Occupancy of the default word-count tokenizer instantiation on the
 // current device, as the runtime sees it (blocks/CU clips the grid; the
 // register count and static LDS are what decide it).
@@ -1327,6 +1395,14 @@ py::dict tokenizer_occupancy() {
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("join_bounds", &join_bounds, py::arg("lkeys"), py::arg("rkeys"),
+        py::arg("window") = true,
+        "(lo, cnt) of each left key in the sorted right keys");
+  m.def("join_bounds_caps", &join_bounds_caps,
+        "(BTILE, WIN) of the windowed join_bounds");
+  m.def("join_expand", &join_expand,
+        "(li, ri) row pairs from the bounds and their exclusive cumsum");
+  m.def("join_caps", &join_caps, "(TILE, LDS_ROWS) of join_expand");
   m.def("tokenizer_occupancy", &tokenizer_occupancy,
         "blocks/CU, registers and static LDS of the default tokenizer");
   m.def("postings_search", &postings_search,

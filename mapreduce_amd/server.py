@@ -105,11 +105,14 @@ class Server:
 
     GPU_REDUCERS = ("sum",)  # fused text engine (wordcount family)
     GPU_PAIR_REDUCERS = ("sum", "min", "max", "minmax")  # keyed-reduce
+    # equi-join of two staged relations: reducer name -> JoinJob how
+    GPU_JOIN_REDUCERS = {"join": "inner", "join_left": "left",
+                         "join_semi": "semi", "join_anti": "anti"}
 
     def _gpu_engine_kind(self) -> Optional[str]:
         """Which GPU engine family this task routes to, or None.
 
-        Five families (one worked example each; README table):
+        Six families (one worked example each; README table):
           "bytes"   mapfn_gpu + reducefn_gpu="sum" — fused tokenize/
                     combine wordcount engine (examples/wordcount)
           "pairs"   mapfn_gpu_pairs + sum/min/max/minmax — keyed
@@ -120,6 +123,8 @@ class Server:
                     (examples/inverted_index)
           "gradsum" mapfn_gpu_grads + "gradsum" — bucketed RCCL
                     gradient allreduce (examples/train_digits, kmeans)
+          "join"    mapfn_gpu_pairs + join/join_left/join_semi/join_anti
+                    — equi-join of two relations (examples/join_tables)
 
         MR_GPU_TIER=off forces host tier; =force routes the GPU data
         path onto the CPU-ops engine (testing without a GPU)."""
@@ -152,6 +157,11 @@ class Server:
             # identity), so no property flags are required — the output
             # contract is global key order (TeraSort family)
             kind = "sort"
+        elif (callable(fns.mapfn_gpu_pairs)
+              and fns.reducefn_gpu in self.GPU_JOIN_REDUCERS):
+            # equi-join: the "reduce" pairs the two relations' rows of a
+            # key, exact by construction — no property flags needed
+            kind = "join"
         elif (callable(fns.mapfn_gpu_pairs)
               and fns.reducefn_gpu in self.GPU_PAIR_REDUCERS
               and fns.associative and fns.commutative
@@ -609,6 +619,130 @@ class Server:
         })
         self.print_stats()
 
+    def _loop_gpu_join(self) -> None:
+        """Equi-join GPU engine: each map job stages rows of ONE of two
+        relations — mapfn_gpu_pairs(key, value) -> (keys, vals, side),
+        side 0 = left, 1 = right — and the reduce pairs the rows of every
+        key (gpu/join.py: stable sorts, mulhi-partitioned all-to-all of
+        both sides, ops.join_sorted).  reducefn_gpu picks the join:
+        "join" (inner), "join_left", "join_semi", "join_anti".
+
+        finalfn receives, per key in global u64 key order,
+        (gpu_key_decode(key), [(lval, rval), ...]) — rval None on the
+        unmatched rows of join_left — or (key, [lval, ...]) under semi
+        and anti.  Rank r owns the r-th contiguous range of the key space
+        (mulhi is monotonic), so the rank-major concatenation is already
+        that order.
+
+        Contract: int64-representable keys; one value column per side,
+        its dtype uniform across the side's map jobs (float -> f64, int
+        -> i64)."""
+        import torch
+
+        from .gpu import dist as dx
+        from .gpu.join import JoinJob
+
+        t_start = gettime()
+        rank, world = dx.world_info()
+        device = (torch.device("cuda", torch.cuda.current_device())
+                  if torch.cuda.is_available() else torch.device("cpu"))
+        op = self.fns.reducefn_gpu
+        how = self.GPU_JOIN_REDUCERS[op]
+        pairwise = how in ("inner", "left")
+        decode = self.fns.gpu_key_decode or (lambda k: k)
+        gtask = Task(self.coord, key="task_gpu")
+        staged = None  # (job signature, lk, lv, rk, rv) — iteration reuse
+        while not self.finished:
+            if rank == 0:
+                gtask.create_collection(TASK_STATUS.WAIT, {
+                    "fns": {"engine": f"join:{how}"},
+                    "storage": "hbm", "result_ns": "result",
+                }, self.iteration)
+            jobs = self._collect_taskfn_jobs()
+            mine = [kv for i, kv in enumerate(jobs) if i % world == rank]
+            if rank == 0:
+                gtask.set_task_status(TASK_STATUS.MAP)
+            sig = [k for k, _ in mine]
+            if staged is None or staged[0] != sig:
+                kcols = ([], [])
+                vcols = ([], [])
+                for k, v in mine:
+                    out = self.fns.mapfn_gpu_pairs(k, v)
+                    if not (isinstance(out, (tuple, list))
+                            and len(out) == 3 and out[2] in (0, 1)):
+                        raise ValueError(
+                            "mapfn_gpu_pairs must return (keys, vals, side) "
+                            f"under reducefn_gpu={op!r}, side 0 for the "
+                            "left relation and 1 for the right; job "
+                            f"{k!r} returned "
+                            + (f"a {len(out)}-tuple"
+                               if isinstance(out, (tuple, list))
+                               else type(out).__name__))
+                    ks, vs, side = out
+                    kcols[side].append(torch.as_tensor(ks,
+                                                       dtype=torch.int64))
+                    # floats stage as f64 from the start (as_tensor's
+                    # default f32 would round them before the widening);
+                    # an empty list is f32 to torch and decides nothing
+                    vt = torch.as_tensor(vs)
+                    vcols[side].append(
+                        torch.as_tensor(vs, dtype=torch.float64)
+                        if vt.is_floating_point() and vt.numel()
+                        else vt.to(torch.int64))
+                # a rank may stage nothing of a side yet receive its rows
+                # in the shuffle: the ranks agree on each side's dtype
+                isf = torch.tensor(
+                    [int(any(c.is_floating_point() for c in vcols[s]))
+                     for s in (0, 1)], dtype=torch.int64, device=device)
+                if world > 1:
+                    import torch.distributed as td
+                    td.all_reduce(isf, op=td.ReduceOp.MAX)
+                cols = []
+                for s, f in zip((0, 1), isf.cpu().tolist()):
+                    dt = torch.float64 if f else torch.int64
+                    cols.append(torch.cat(kcols[s]).to(device) if kcols[s]
+                                else torch.empty(0, dtype=torch.int64,
+                                                 device=device))
+                    cols.append(torch.cat(vcols[s]).to(dt).to(device)
+                                if vcols[s]
+                                else torch.empty(0, dtype=dt, device=device))
+                staged = (sig, *cols)
+            _, lk, lv, rk, rv = staged
+            if rank == 0:
+                gtask.set_task_status(TASK_STATUS.REDUCE)
+            res = JoinJob(device, how=how).run(lk, lv, rk, rv)
+            if rank == 0:
+                gtask.set_task_status(TASK_STATUS.FINISHED)
+            # one tolist() per column, then group the rows of each key
+            keys = res.keys.cpu().tolist()
+            rows = res.lvals.cpu().tolist()
+            if pairwise:
+                rvs = res.rvals.cpu().tolist()
+                if how == "left":
+                    rvs = [r if m else None for r, m in
+                           zip(rvs, res.matched.cpu().tolist())]
+                rows = list(zip(rows, rvs))
+            pairs = []
+            last = None
+            for k, row in zip(keys, rows):
+                if not pairs or k != last:
+                    pairs.append((decode(k), []))
+                    last = k
+                pairs[-1][1].append(row)
+            # rank-major concatenation IS global key order: no re-sort
+            reply = self._gpu_finalize_round(pairs, rank, world)
+            if reply == "loop":
+                self.iteration += 1
+                self._log(f"iterative loop -> iteration {self.iteration}")
+            else:
+                self.finished = True
+        self.stats.update({
+            "tier": "gpu", "engine": "join",
+            "map_failed": 0, "reduce_failed": 0,
+            "total_time": gettime() - t_start,
+        })
+        self.print_stats()
+
     # ------------------------------------------------------------ map phase
     def _prepare_map(self) -> None:
         """server_prepare_map (server.lua:249-276): run taskfn(emit), check
@@ -788,6 +922,7 @@ class Server:
             fn = {"bytes": self._loop_gpu,
                   "pairs": self._loop_gpu_pairs,
                   "sort": self._loop_gpu_sort,
+                  "join": self._loop_gpu_join,
                   "index": self._loop_gpu_index,
                   "gradsum": self._loop_gpu_grads}[kind]
             try:
