@@ -719,3 +719,275 @@ def join_sorted(lkeys: torch.Tensor, rkeys: torch.Tensor,
     if max_rows is not None and total > max_rows:
         raise JoinTooLarge(total, max_rows)
     return tuple(ext().join_expand(off, lo, cnt, total))
+
+
+# ---------------------------------------------------------------------------
+# per-key order statistics over key-sorted rows (K4/K5 for reducers that
+# need the whole value list of a key: quantiles, top-k, distinct counts)
+# ---------------------------------------------------------------------------
+
+# caps of the group kernels (ops/hip/group.hip): rows per LDS-sorted tile,
+# rank specifications per pick launch.  The CPU tier has no tiles; it
+# reports the same values so tests size their cases alike on both tiers.
+GROUP_TILE = 2048
+GROUP_QMAX = 8
+# the tile kernel orders a tile whose segments are all this short by rank
+# counting and runs the bitonic network otherwise; tests size cases by it
+GROUP_RANK_MAX = 256
+GROUP_MAX_DEN = 10 ** 6
+GROUP_MAX_ROWS = 2 ** 31
+
+
+def group_caps():
+    """-> (GROUP_TILE, GROUP_QMAX): the extension's own values on a GPU
+    machine, the Python constants above on the CPU tier."""
+    if torch.cuda.is_available():
+        return tuple(int(c) for c in ext().group_caps())
+    return GROUP_TILE, GROUP_QMAX
+
+
+def group_rank_max() -> int:
+    """-> GROUP_RANK_MAX, from the extension on a GPU machine."""
+    if torch.cuda.is_available():
+        return int(ext().group_rank_max())
+    return GROUP_RANK_MAX
+
+
+def _group_vals_i64(vals: torch.Tensor, name: str = "vals"):
+    """-> (int64 view, is f64) of an i64 or f64 value column."""
+    if vals.dtype == torch.float64:
+        return vals.view(torch.int64), True
+    if vals.dtype == torch.int64:
+        return vals, False
+    raise TypeError(f"{name} must be int64 or float64, got {vals.dtype}")
+
+
+def _group_check_rows(n: int) -> None:
+    if n >= GROUP_MAX_ROWS:
+        raise ValueError(f"group ops take fewer than 2^31 rows, got {n}")
+
+
+def group_order_keys(vals: torch.Tensor) -> torch.Tensor:
+    """The u64 order key of each i64 or f64 value, as an i64 bit pattern:
+    i64 bits ^ 2^63; f64 the sign-flip transform with -0.0 keyed as +0.0
+    and every NaN keyed above +inf.  Values with equal order keys are equal
+    to every group op."""
+    v, f64 = _group_vals_i64(vals)
+    if not vals.is_cuda:
+        from . import _cpu
+        return _cpu._from_u64(_cpu.group_order_keys(vals))
+    return ext().group_order_keys(v.contiguous(), f64)
+
+
+def group_by_key_sorted(keys: torch.Tensor):
+    """keys sorted (u64 bit order) -> (ukeys i64[nseg], offsets
+    i64[nseg + 1]): segment s is rows offsets[s]:offsets[s + 1].  One host
+    sync (the segment count)."""
+    _group_check_rows(keys.numel())
+    if not keys.is_cuda:
+        from . import _cpu
+        return _cpu.group_by_key_sorted(keys)
+    keys = keys.contiguous()
+    return _group_offsets(keys, ext().head_flags(keys))
+
+
+def _group_offsets(keys, flags):
+    n = keys.numel()
+    heads = torch.nonzero(flags).squeeze(1)
+    offsets = torch.empty(heads.numel() + 1, dtype=torch.int64,
+                          device=keys.device)
+    offsets[:-1] = heads
+    offsets[-1] = n
+    return keys.index_select(0, heads), offsets
+
+
+def _group_two_sort(keys, v, f64):
+    """The composition: sort by order key, then stably by key."""
+    ok = ext().group_order_keys(v, f64)
+    _, k1, v1 = sort_by_key(ok, keys, v)
+    _, v2 = sort_by_key(k1, v1)
+    return v2
+
+
+def group_straddlers(offsets: torch.Tensor, tile: int):
+    """-> (sidx i64[ns], rows): the segments that cross a boundary between
+    tiles of `tile` rows (start // tile != (end - 1) // tile) and the
+    number of rows they hold.  One host sync."""
+    st, en = offsets[:-1], offsets[1:]
+    smask = torch.div(st, tile, rounding_mode="floor") != torch.div(
+        en - 1, tile, rounding_mode="floor")
+    sidx = torch.nonzero(smask).squeeze(1)
+    rows = int((en - st).index_select(0, sidx).sum().item()) \
+        if sidx.numel() else 0
+    return sidx, rows
+
+
+def sort_values_in_groups(keys_sorted: torch.Tensor, vals: torch.Tensor,
+                          offsets: Optional[torch.Tensor] = None):
+    """The value column ordered within every key: keys_sorted ascending in
+    u64 bit order (the caller's contract), vals i64 or f64, one per key; the
+    dtype is kept and the inputs are never written.  Order is that of
+    group_order_keys; values with equal order keys keep their input order.
+    offsets: what group_by_key_sorted returned for these keys, when the
+    caller holds it.
+
+    Device path: every tile of GROUP_TILE rows is sorted in LDS by (segment,
+    order key) — by rank counting where the tile's segments are at most
+    GROUP_RANK_MAX long, by a bitonic network otherwise — which finishes the
+    segments inside one tile; the rows of
+    segments that cross a tile boundary are compacted, sorted with
+    sort_by_key (order key, then stably their segment number, a pass or two
+    since few segments are that long) and copied over their slots; when
+    every row is in such a segment the tile pass is skipped.  This path
+    measured faster than the composition at every share of such rows
+    (profiles/grouped.md), so nothing dispatches on the share.  Under
+    MR_GROUP_TWO_SORT=1 (read per call) the composition runs instead: sort
+    by order key, then stably by key.  Two host syncs (the segments, the
+    straddlers)."""
+    n = keys_sorted.numel()
+    if vals.numel() != n:
+        raise ValueError("one value per key required")
+    _group_check_rows(n)
+    v, f64 = _group_vals_i64(vals)
+    if not keys_sorted.is_cuda and not vals.is_cuda:
+        if keys_sorted.dtype != torch.int64:
+            raise TypeError("keys must be int64")
+        from . import _cpu
+        return _cpu.sort_values_in_groups(keys_sorted, vals)
+    import os
+    keys = keys_sorted.contiguous()
+    v = v.contiguous()
+    if os.environ.get("MR_GROUP_TWO_SORT", "0") == "1":
+        return _group_two_sort(keys, v, f64).view(vals.dtype)
+    if n == 0:
+        ext().group_tile_sort(keys, v, f64)  # the host checks still run
+        return vals.clone()
+    e = ext()
+    flags = e.head_flags(keys)
+    seg = torch.cumsum(flags, 0)
+    if offsets is None:
+        _, offsets = _group_offsets(keys, flags)
+    tile = group_caps()[0]
+    sidx, rows = group_straddlers(offsets, tile)
+    # all rows in straddlers: every slot is overwritten below
+    out = e.group_tile_sort(seg, v, f64) if rows < n else torch.empty_like(v)
+    if rows:
+        ns = sidx.numel()
+        sst = offsets.index_select(0, sidx)
+        slen = offsets.index_select(0, sidx + 1) - sst
+        first = torch.cumsum(slen, 0) - slen  # of each straddler, compacted
+        snum = torch.repeat_interleave(
+            torch.arange(ns, device=keys.device), slen, output_size=rows)
+        ridx = (torch.arange(rows, device=keys.device)
+                + (sst - first).index_select(0, snum))
+        sv = v.index_select(0, ridx)
+        _, snum, sv = sort_by_key(e.group_order_keys(sv, f64), snum, sv)
+        _, sv = sort_by_key(snum, sv, bits=max(1, (ns - 1).bit_length()))
+        out.index_copy_(0, ridx, sv)
+    return out.view(vals.dtype)
+
+
+def _group_rank_specs(fracs, interpolation: str):
+    """-> [(num, den, higher)] after the checks of group_quantiles."""
+    import fractions
+    if interpolation not in ("lower", "higher"):
+        raise ValueError("interpolation must be 'lower' or 'higher', got "
+                         f"{interpolation!r}")
+    fracs = list(fracs)
+    qmax = group_caps()[1]
+    if not 1 <= len(fracs) <= qmax:
+        raise ValueError(f"Q must be in [1, {qmax}], got {len(fracs)}")
+    specs = []
+    for f in fracs:
+        if isinstance(f, fractions.Fraction):
+            num, den = f.numerator, f.denominator
+        elif (isinstance(f, (tuple, list)) and len(f) == 2
+              and all(isinstance(x, int) and not isinstance(x, bool)
+                      for x in f)):
+            num, den = f
+        else:
+            raise TypeError(
+                "fracs must be (num, den) integer pairs or Fractions, got "
+                f"{f!r}: a float's index is not exact")
+        if not 1 <= den <= GROUP_MAX_DEN:
+            raise ValueError(f"den must be in [1, 10^6], got {den}")
+        if not 0 <= num <= den:
+            raise ValueError(f"num must be in [0, den], got {num}/{den}")
+        specs.append((int(num), int(den), interpolation == "higher"))
+    return specs
+
+
+def _group_check_offsets(offsets: torch.Tensor) -> None:
+    if offsets.dtype != torch.int64:
+        raise TypeError("offsets must be int64")
+    if offsets.numel() < 1:
+        raise ValueError("offsets holds nseg + 1 entries")
+
+
+def group_quantiles(offsets: torch.Tensor, sorted_vals: torch.Tensor, fracs,
+                    interpolation: str = "lower") -> torch.Tensor:
+    """-> [nseg, Q] in the values' dtype: for each segment of the ordered
+    value column (sort_values_in_groups) and each fraction num/den the value
+    at index (num * (len - 1) + (den - 1 if higher else 0)) // den, in exact
+    integer arithmetic.  fracs: (num, den) integer pairs or
+    fractions.Fraction, 0 <= num <= den <= 10^6, at most GROUP_QMAX of them;
+    floats are refused.  No host sync."""
+    specs = _group_rank_specs(fracs, interpolation)
+    _group_check_offsets(offsets)
+    _group_check_rows(sorted_vals.numel())
+    v, _ = _group_vals_i64(sorted_vals, "sorted_vals")
+    if not offsets.is_cuda and not sorted_vals.is_cuda:
+        from . import _cpu
+        return _cpu.group_pick(offsets, sorted_vals, specs)
+    out = ext().group_pick(offsets.contiguous(), v.contiguous(),
+                           [s[0] for s in specs], [s[1] for s in specs],
+                           [s[2] for s in specs])
+    return out.view(sorted_vals.dtype)
+
+
+def group_topk(offsets: torch.Tensor, sorted_vals: torch.Tensor, k: int,
+               largest: bool = True):
+    """-> (vals [nseg, k], n i64[nseg] = min(k, len)): the k largest values
+    of each ordered segment, descending (NaN first), or the k smallest,
+    ascending.  Unused slots hold 0.  No host sync."""
+    k = int(k)
+    if k < 1:
+        raise ValueError(f"k must be at least 1, got {k}")
+    _group_check_offsets(offsets)
+    _group_check_rows(sorted_vals.numel())
+    _group_vals_i64(sorted_vals, "sorted_vals")
+    st, en = offsets[:-1], offsets[1:]
+    lens = en - st
+    j = torch.arange(k, device=offsets.device)
+    pos = (en - 1).unsqueeze(1) - j if largest else st.unsqueeze(1) + j
+    used = j < lens.unsqueeze(1)
+    if sorted_vals.numel():
+        out = sorted_vals[pos.clamp(0, sorted_vals.numel() - 1)]
+        out = torch.where(used, out, torch.zeros_like(out))
+    else:
+        out = torch.zeros(pos.shape, dtype=sorted_vals.dtype,
+                          device=sorted_vals.device)
+    return out, lens.clamp(max=k)
+
+
+def group_distinct_flags(keys_sorted: torch.Tensor,
+                         sorted_vals: torch.Tensor) -> torch.Tensor:
+    """flags i64[n]: 1 where a row starts a segment or its order key
+    differs from the previous row's (values ordered within each key)."""
+    if sorted_vals.numel() != keys_sorted.numel():
+        raise ValueError("one value per key required")
+    _group_check_rows(keys_sorted.numel())
+    v, f64 = _group_vals_i64(sorted_vals, "sorted_vals")
+    if not keys_sorted.is_cuda and not sorted_vals.is_cuda:
+        from . import _cpu
+        return _cpu.group_distinct_flags(keys_sorted, sorted_vals)
+    return ext().group_distinct_flags(keys_sorted.contiguous(),
+                                      v.contiguous(), f64)
+
+
+def group_distinct(keys_sorted: torch.Tensor,
+                   sorted_vals: torch.Tensor) -> torch.Tensor:
+    """-> counts i64[nseg]: the number of distinct values (order keys) of
+    each key; +0.0 and -0.0 count once, all NaNs count once."""
+    flags = group_distinct_flags(keys_sorted, sorted_vals)
+    return reduce_by_key_sorted(keys_sorted, flags, op="sum")[1]

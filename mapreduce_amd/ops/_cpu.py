@@ -357,3 +357,61 @@ def join_sorted(lkeys: torch.Tensor, rkeys: torch.Tensor, how: str,
     ri = lo[li] + (np.arange(total, dtype=np.int64) - off[li])
     ri[cnt[li] == 0] = -1
     return torch.from_numpy(li), torch.from_numpy(ri)
+
+
+# ---- per-key order statistics ---------------------------------------------
+
+_SIGN = np.uint64(1 << 63)
+_ONES = np.uint64(_MASK64)
+
+
+def group_order_keys(vals: torch.Tensor) -> np.ndarray:
+    """u64 order key of each i64 / f64 value: i64 bits ^ 2^63; f64 the
+    sign-flip transform with -0.0 keyed as +0.0 and every NaN keyed above
+    +inf (all ones)."""
+    if vals.dtype == torch.int64:
+        return _u64(vals.contiguous()) ^ _SIGN
+    if vals.dtype != torch.float64:
+        raise TypeError(f"vals must be int64 or float64, got {vals.dtype}")
+    b = _u64(vals.contiguous().view(torch.int64)).copy()
+    b[(b << np.uint64(1)) == 0] = 0
+    nan = (b & ~_SIGN) > np.uint64(0x7FF0000000000000)
+    ok = b ^ np.where((b & _SIGN) != 0, _ONES, _SIGN)
+    ok[nan] = _ONES
+    return ok
+
+
+def group_by_key_sorted(keys: torch.Tensor):
+    ku = _u64(keys.contiguous())
+    n = len(ku)
+    heads = np.flatnonzero(np.concatenate(
+        [np.ones(min(n, 1), dtype=bool), ku[1:] != ku[:-1]]))
+    offsets = np.concatenate([heads, [n]]).astype(np.int64)
+    return _from_u64(ku[heads]), torch.from_numpy(offsets)
+
+
+def sort_values_in_groups(keys: torch.Tensor, vals: torch.Tensor):
+    """np.lexsort (stable) on (key, order key): equal values keep their
+    input order, as on the device."""
+    order = np.lexsort((group_order_keys(vals), _u64(keys.contiguous())))
+    return vals[torch.from_numpy(order.astype(np.int64))]
+
+
+def group_pick(offsets: torch.Tensor, vals: torch.Tensor, specs):
+    off = offsets.numpy()
+    start, length = off[:-1], off[1:] - off[:-1]
+    out = torch.zeros((len(start), len(specs)), dtype=vals.dtype)
+    for q, (num, den, higher) in enumerate(specs):
+        idx = (num * (length - 1) + (den - 1 if higher else 0)) // den
+        ok = length > 0
+        out[torch.from_numpy(ok), q] = vals[torch.from_numpy(
+            (start + idx)[ok])]
+    return out
+
+
+def group_distinct_flags(keys: torch.Tensor, vals: torch.Tensor):
+    ku = _u64(keys.contiguous())
+    ok = group_order_keys(vals)
+    flags = np.ones(len(ku), dtype=np.int64)
+    flags[1:] = (ku[1:] != ku[:-1]) | (ok[1:] != ok[:-1])
+    return torch.from_numpy(flags)

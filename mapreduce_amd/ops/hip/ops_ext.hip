@@ -15,6 +15,7 @@
 #include <utility>
 
 #include "gradsum.hip"
+#include "group.hip"
 #include "join.hip"
 #include "lex_order.hip"
 #include "mr_kernels.hip"
@@ -1378,6 +1379,118 @@ std::vector<torch::Tensor> join_expand(torch::Tensor off, torch::Tensor lo,
   return {li, ri};
 }
 
+// ------------------------------------------------- per-key order statistics
+// caps of the group kernels: (rows per tile, rank specifications per pick)
+std::vector<long> group_caps() { return {GROUP_TILE, GROUP_QMAX}; }
+
+// the longest segment the tile kernel's rank-counting pass takes; a tile
+// holding a longer one to finish runs the bitonic network
+long group_rank_max() { return GROUP_RANK_MAX; }
+
+namespace {
+void check_group_rows(long n) {
+  TORCH_CHECK(n < (1L << 31), "group ops take fewer than 2^31 rows, got ", n);
+}
+}  // namespace
+
+// the u64 order key of each value (int64 view of an i64 or f64 column)
+torch::Tensor group_order_keys(torch::Tensor vals, bool f64) {
+  check_dev_i64(vals, "vals");
+  long n = vals.numel();
+  check_group_rows(n);
+  auto out = torch::empty({n}, vals.options());
+  if (n)
+    hipLaunchKernelGGL(group_order_keys_kernel, dim3(grid_for(n)),
+                       dim3(GROUP_BLOCK), 0, cur_stream(), u64cp(vals), n,
+                       (int)f64, u64p(out));
+  return out;
+}
+
+// seg i64[n]: nondecreasing segment id of every key-sorted row.  -> a fresh
+// column with the values of every segment that lies inside one tile of
+// GROUP_TILE rows in order; rows of other segments are unspecified (a tile
+// inside one such segment is not written at all).  No host sync.
+torch::Tensor group_tile_sort(torch::Tensor seg, torch::Tensor vals,
+                              bool f64) {
+  check_dev_i64(seg, "seg");
+  check_dev_i64(vals, "vals");
+  TORCH_CHECK(seg.device() == vals.device(),
+              "seg and vals must be on the same device");
+  long n = vals.numel();
+  TORCH_CHECK(seg.numel() == n, "seg must hold one segment id per value");
+  check_group_rows(n);
+  auto out = torch::empty({n}, vals.options());
+  if (n) {
+    long ntiles = (n + GROUP_TILE - 1) / GROUP_TILE;
+    hipLaunchKernelGGL(group_tile_sort_kernel, dim3(ntiles),
+                       dim3(GROUP_BLOCK), 0, cur_stream(),
+                       seg.data_ptr<i64>(), u64cp(vals), n, (int)f64,
+                       u64p(out));
+  }
+  return out;
+}
+
+// out[s, q] = vals[off[s] + (num[q] * (len - 1) + add[q]) / den[q]], add =
+// den - 1 where higher[q] else 0; 0 for an empty segment.  No host sync.
+torch::Tensor group_pick(torch::Tensor offsets, torch::Tensor vals,
+                         std::vector<long> num, std::vector<long> den,
+                         std::vector<bool> higher) {
+  check_dev_i64(offsets, "offsets");
+  check_dev_i64(vals, "vals");
+  TORCH_CHECK(offsets.device() == vals.device(),
+              "offsets and vals must be on the same device");
+  TORCH_CHECK(offsets.numel() >= 1, "offsets holds nseg + 1 entries");
+  long nq = (long)num.size();
+  TORCH_CHECK(nq >= 1 && nq <= GROUP_QMAX, "Q must be in [1, ", GROUP_QMAX,
+              "], got ", nq);
+  TORCH_CHECK((long)den.size() == nq && (long)higher.size() == nq,
+              "num, den and higher must have one entry per specification");
+  long n = vals.numel();
+  check_group_rows(n);
+  GroupSpecs sp;
+  for (long q = 0; q < nq; ++q) {
+    TORCH_CHECK(den[q] >= 1 && den[q] <= 1000000,
+                "den must be in [1, 10^6], got ", den[q]);
+    TORCH_CHECK(num[q] >= 0 && num[q] <= den[q],
+                "num must be in [0, den], got ", num[q], "/", den[q]);
+    sp.num[q] = (u32)num[q];
+    sp.den[q] = (u32)den[q];
+    sp.add[q] = higher[q] ? (u32)(den[q] - 1) : 0u;
+  }
+  for (long q = nq; q < GROUP_QMAX; ++q) {
+    sp.num[q] = 0;
+    sp.den[q] = 1;
+    sp.add[q] = 0;
+  }
+  long nseg = offsets.numel() - 1;
+  auto out = torch::empty({nseg, nq}, vals.options());
+  if (nseg)
+    hipLaunchKernelGGL(group_pick_kernel, dim3(grid_for(nseg * nq)),
+                       dim3(GROUP_BLOCK), 0, cur_stream(),
+                       offsets.data_ptr<i64>(), nseg, u64cp(vals), n, sp,
+                       (int)nq, u64p(out));
+  return out;
+}
+
+// flags i64[n]: 1 where a key-sorted row starts a segment or its order key
+// differs from the previous row's.  No host sync.
+torch::Tensor group_distinct_flags(torch::Tensor keys, torch::Tensor vals,
+                                   bool f64) {
+  check_dev_i64(keys, "keys");
+  check_dev_i64(vals, "vals");
+  TORCH_CHECK(keys.device() == vals.device(),
+              "keys and vals must be on the same device");
+  long n = keys.numel();
+  TORCH_CHECK(vals.numel() == n, "vals must hold one value per key");
+  check_group_rows(n);
+  auto flags = torch::empty({n}, keys.options());
+  if (n)
+    hipLaunchKernelGGL(group_distinct_flags_kernel, dim3(grid_for(n)),
+                       dim3(GROUP_BLOCK), 0, cur_stream(), u64cp(keys),
+                       u64cp(vals), n, (int)f64, flags.data_ptr<i64>());
+  return flags;
+}
+
 // Occupancy of the default word-count tokenizer instantiation on the
 // current device, as the runtime sees it (blocks/CU clips the grid; the
 // register count and static LDS are what decide it).
@@ -1395,6 +1508,17 @@ py::dict tokenizer_occupancy() {
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("group_caps", &group_caps, "(TILE, QMAX) of the group kernels");
+  m.def("group_rank_max", &group_rank_max,
+        "longest segment of the tile kernel's rank-counting pass");
+  m.def("group_order_keys", &group_order_keys,
+        "u64 order key of each i64 / f64 value");
+  m.def("group_tile_sort", &group_tile_sort,
+        "values ordered inside every segment that fits one tile");
+  m.def("group_pick", &group_pick,
+        "values at exact rank fractions of each ordered segment");
+  m.def("group_distinct_flags", &group_distinct_flags,
+        "1 where a row starts a segment or a new value");
   m.def("join_bounds", &join_bounds, py::arg("lkeys"), py::arg("rkeys"),
         py::arg("window") = true,
         "(lo, cnt) of each left key in the sorted right keys");

@@ -86,6 +86,8 @@ class Server:
         self.stall_timeout = params.get("stall_timeout", 600.0)
         self.verbose = params.get("verbose", True)
         self.fns = FnSet(fns, self.params["init_args"])
+        # a malformed "group" family reducer is refused here, not mid-task
+        self.parse_group_reducer(self.fns.reducefn_gpu)
         self.fs = fsmod.router(storage, self.params["path"])
         return self
 
@@ -108,11 +110,52 @@ class Server:
     # equi-join of two staged relations: reducer name -> JoinJob how
     GPU_JOIN_REDUCERS = {"join": "inner", "join_left": "left",
                          "join_semi": "semi", "join_anti": "anti"}
+    # per-key order statistics: reducers over the whole value list of a key
+    GPU_GROUP_REDUCERS = ("group", "median", "quantile", "topk", "bottomk",
+                          "distinct")
+
+    @classmethod
+    def parse_group_reducer(cls, name):
+        """reducefn_gpu of the "group" family -> (op, parameter), or None
+        when the name belongs to another family.  "group", "median" and
+        "distinct" take no parameter; "quantile:N/D[,N/D...]" gives a list
+        of (N, D); "topk:K" and "bottomk:K" give K.  A malformed parameter
+        raises ValueError naming the string."""
+        if not isinstance(name, str):
+            return None
+        op, sep, arg = name.partition(":")
+        if op not in cls.GPU_GROUP_REDUCERS:
+            return None
+        bad = ValueError(
+            f"malformed reducefn_gpu {name!r}: expected 'group', 'median', "
+            "'distinct', 'quantile:N/D[,N/D...]' with 0 <= N <= D <= 10^6 "
+            "(at most 8), 'topk:K' or 'bottomk:K' with K >= 1")
+        if op in ("group", "median", "distinct"):
+            if sep:
+                raise bad
+            return op, None
+        if op in ("topk", "bottomk"):
+            if not (arg.isascii() and arg.isdigit() and int(arg) >= 1):
+                raise bad
+            return op, int(arg)
+        fracs = []
+        for part in arg.split(","):
+            n, slash, d = part.partition("/")
+            if not (slash and n.isascii() and n.isdigit() and d.isascii()
+                    and d.isdigit()):
+                raise bad
+            fracs.append((int(n), int(d)))
+        from . import ops
+        if not 1 <= len(fracs) <= ops.GROUP_QMAX or any(
+                not (1 <= d <= ops.GROUP_MAX_DEN and n <= d)
+                for n, d in fracs):
+            raise bad
+        return op, fracs
 
     def _gpu_engine_kind(self) -> Optional[str]:
         """Which GPU engine family this task routes to, or None.
 
-        Six families (one worked example each; README table):
+        Seven families (one worked example each; README table):
           "bytes"   mapfn_gpu + reducefn_gpu="sum" — fused tokenize/
                     combine wordcount engine (examples/wordcount)
           "pairs"   mapfn_gpu_pairs + sum/min/max/minmax — keyed
@@ -125,6 +168,9 @@ class Server:
                     gradient allreduce (examples/train_digits, kmeans)
           "join"    mapfn_gpu_pairs + join/join_left/join_semi/join_anti
                     — equi-join of two relations (examples/join_tables)
+          "group"   mapfn_gpu_pairs + group/median/quantile:N/D,.../
+                    topk:K/bottomk:K/distinct — per-key order statistics
+                    over the whole value list (examples/percentiles)
 
         MR_GPU_TIER=off forces host tier; =force routes the GPU data
         path onto the CPU-ops engine (testing without a GPU)."""
@@ -162,6 +208,11 @@ class Server:
             # equi-join: the "reduce" pairs the two relations' rows of a
             # key, exact by construction — no property flags needed
             kind = "join"
+        elif (callable(fns.mapfn_gpu_pairs)
+              and self.parse_group_reducer(fns.reducefn_gpu) is not None):
+            # reducers over the whole value list of a key: not
+            # associative, so there are no property flags to require
+            kind = "group"
         elif (callable(fns.mapfn_gpu_pairs)
               and fns.reducefn_gpu in self.GPU_PAIR_REDUCERS
               and fns.associative and fns.commutative
@@ -743,6 +794,107 @@ class Server:
         })
         self.print_stats()
 
+    def _loop_gpu_group(self) -> None:
+        """Order-statistics GPU engine: the task's emitted (key, value)
+        pairs are staged as device columns (mapfn_gpu_pairs, as for the
+        keyed-reduce engine), grouped by key with the values of every key
+        in order (gpu/grouped.py: sort, mulhi-partitioned all-to-all,
+        ops.sort_values_in_groups) and reduced by reducefn_gpu:
+
+          "group"                  (key, [values ascending])
+          "median", one quantile   (key, [v])
+          several quantiles        (key, [(v1, ..., vQ)])
+          "topk:K" / "bottomk:K"   (key, [v1, ..., vm]), m = min(K, len),
+                                   descending / ascending
+          "distinct"               (key, [count])
+
+        Quantiles pick the value at index (N * (len - 1)) // D of the
+        ordered list.  topk, bottomk and distinct trim the lists before
+        the exchange (GroupedValuesJob combine).  finalfn receives the
+        pairs in global u64 key order: rank r owns the r-th contiguous
+        range of the key space.
+
+        Contract: int64-representable keys; the value dtype uniform across
+        ranks (float -> f64, int -> i64)."""
+        import torch
+
+        from .gpu import dist as dx
+        from .gpu.grouped import GroupedValuesJob
+
+        t_start = gettime()
+        rank, world = dx.world_info()
+        device = (torch.device("cuda", torch.cuda.current_device())
+                  if torch.cuda.is_available() else torch.device("cpu"))
+        name = self.fns.reducefn_gpu
+        op, arg = self.parse_group_reducer(name)
+        combine = {"topk": ("topk", arg), "bottomk": ("bottomk", arg),
+                   "distinct": "distinct"}.get(op)
+        decode = self.fns.gpu_key_decode or (lambda k: k)
+        gtask = Task(self.coord, key="task_gpu")
+        staged = None  # (job signature, keys, vals) — iteration reuse
+        while not self.finished:
+            if rank == 0:
+                gtask.create_collection(TASK_STATUS.WAIT, {
+                    "fns": {"engine": f"group:{op}"},
+                    "storage": "hbm", "result_ns": "result",
+                }, self.iteration)
+            jobs = self._collect_taskfn_jobs()
+            mine = [kv for i, kv in enumerate(jobs) if i % world == rank]
+            if rank == 0:
+                gtask.set_task_status(TASK_STATUS.MAP)
+            sig = [k for k, _ in mine]
+            if staged is None or staged[0] != sig:
+                kcols, vcols = [], []
+                for k, v in mine:
+                    ks, vs = self.fns.mapfn_gpu_pairs(k, v)
+                    kcols.append(torch.as_tensor(ks, dtype=torch.int64))
+                    # floats stage as f64 from the start: as_tensor's
+                    # default (f32) would round them before the widening
+                    vt = torch.as_tensor(vs)
+                    vcols.append(torch.as_tensor(vs, dtype=torch.float64)
+                                 if vt.is_floating_point()
+                                 else vt.to(torch.int64))
+                if kcols:
+                    keys = torch.cat(kcols).to(device)
+                    vals = torch.cat(vcols).to(device)
+                else:
+                    keys = torch.empty(0, dtype=torch.int64, device=device)
+                    vals = torch.empty(0, dtype=torch.float64,
+                                       device=device)
+                staged = (sig, keys, vals)
+            _, keys, vals = staged
+            if rank == 0:
+                gtask.set_task_status(TASK_STATUS.REDUCE)
+            res = GroupedValuesJob(device, combine=combine).run(keys, vals)
+            ukeys = [decode(int(k)) for k in res.keys.cpu().tolist()]
+            if op == "group":
+                lists = [vs for _, vs in res.to_host()]
+            elif op in ("median", "quantile"):
+                rows = res.quantiles(arg or [(1, 2)]).cpu().tolist()
+                lists = [[r[0]] if len(r) == 1 else [tuple(r)] for r in rows]
+            elif op == "distinct":
+                lists = [[c] for c in res.distinct().cpu().tolist()]
+            else:
+                top, m = res.topk(arg, largest=(op == "topk"))
+                lists = [r[:c] for r, c in zip(top.cpu().tolist(),
+                                               m.cpu().tolist())]
+            pairs = list(zip(ukeys, lists))
+            if rank == 0:
+                gtask.set_task_status(TASK_STATUS.FINISHED)
+            # rank-major concatenation IS global key order: no re-sort
+            reply = self._gpu_finalize_round(pairs, rank, world)
+            if reply == "loop":
+                self.iteration += 1
+                self._log(f"iterative loop -> iteration {self.iteration}")
+            else:
+                self.finished = True
+        self.stats.update({
+            "tier": "gpu", "engine": f"group:{op}",
+            "map_failed": 0, "reduce_failed": 0,
+            "total_time": gettime() - t_start,
+        })
+        self.print_stats()
+
     # ------------------------------------------------------------ map phase
     def _prepare_map(self) -> None:
         """server_prepare_map (server.lua:249-276): run taskfn(emit), check
@@ -923,6 +1075,7 @@ class Server:
                   "pairs": self._loop_gpu_pairs,
                   "sort": self._loop_gpu_sort,
                   "join": self._loop_gpu_join,
+                  "group": self._loop_gpu_group,
                   "index": self._loop_gpu_index,
                   "gradsum": self._loop_gpu_grads}[kind]
             try:
