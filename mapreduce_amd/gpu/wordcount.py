@@ -10,10 +10,12 @@ Per step (= one full MapReduce job over the rank's corpus):
                 drops the allocator's pads) + per-bucket LDS count
                 (bucket_count) drains them — every per-word atomic is an
                 LDS atomic.
-  EXTRACT+SORT  table -> unique (hash, count, exemplar pos); sort by hash
-                (K1; sub-1M arrays via one stable torch.sort dispatch) —
-                with mulhi partitioning, the sorted array is
-                partition-contiguous.
+  EXTRACT+SORT  table -> unique (hash, count, exemplar pos) sorted by hash,
+                in one native op (ops.extract_sorted: table keys are
+                unique, so MSD bins + rank counting; it also leaves the
+                word lengths, their offsets and the blob size for the
+                shuffle and for materialize()) — with mulhi partitioning,
+                the sorted array is partition-contiguous.
   SHUFFLE       RCCL all-to-all of (hash, count, exemplar len/bytes) slices
                 (C5/C6): one collective per array over the 7 xGMI links.
   REDUCE        sort the received runs + segmented reduce-by-key (K4->K1+K5),
@@ -49,6 +51,14 @@ class WordCountResult:
     nwords: int             # words processed by this rank this step
     hash_kind: str = "wordhash64"  # GPU tier: wordhash64; CPU test tier:
                                    # fnv1a64 (ops/_cpu.py tokenize_words)
+    # what ops.extract_sorted already computed for (keys, counts, pos),
+    # kept so materialize() need not recompute it: the contiguous
+    # [keys | counts | lens] buffer, the exclusive scan of lens and its
+    # end, and the blob_src they belong to (None: nothing cached)
+    packed: Optional[torch.Tensor] = None
+    offs: Optional[torch.Tensor] = None
+    total_bytes: Optional[int] = None
+    cache_src: Optional[torch.Tensor] = None
 
     def attach_ready_event(self, stream) -> None:
         """Producer on a SIDE stream (the job pipeline) marks when the
@@ -174,10 +184,19 @@ class WordCountResult:
         complete (how bench.py uses it).  Returns (keys_cpu, counts_cpu,
         lens_cpu, blob_cpu)."""
         self._wait_ready()  # no-op for the producer's own in-stream call
-        keys, counts, pos = self._ordered(order)
-        lens, blob = ops.extract_words(self.blob_src, pos)
-        n = keys.numel()
-        packed = torch.cat([keys, counts, lens])
+        n = self.keys.numel()
+        if (order == "hash" and self.packed is not None
+                and self.cache_src is self.blob_src
+                and self.packed.numel() == 3 * n):
+            # extract_sorted left the packed buffer, the offsets and the
+            # blob size: one gather, no scan, no sync, no cat
+            packed = self.packed
+            blob = ops.gather_words(self.blob_src, self.pos, self.offs,
+                                    self.total_bytes)
+        else:
+            keys, counts, pos = self._ordered(order)
+            lens, blob = ops.extract_words(self.blob_src, pos)
+            packed = torch.cat([keys, counts, lens])
         if packed.is_cuda:
             host = torch.empty(packed.shape, dtype=packed.dtype,
                                pin_memory=True)
@@ -584,14 +603,18 @@ class WordCountJob:
         dev = self.device
         self.last_shuffle_rounds = 1
 
-        # ---- EXTRACT + SORT
-        uk, uv, up = self.table.extract()
-        sk, sv, sp = ops.sort_by_key(uk, uv, up)
+        # ---- EXTRACT + SORT: one native op from the table to the sorted,
+        # packed result; it also leaves the word lengths, their offsets
+        # and the blob size (MR_EXTRACT_SORTED=0: the composed general
+        # ops, same tuple)
+        sk, sv, sp, lens, offs, total_b, packed = ops.extract_sorted(
+            self.table)
+        cache = None
 
         if self.world > 1 or dx.force_collectives():
             # ---- SHUFFLE (C5/C6): slice sorted arrays by partition
             counts_d = ops.partition_counts(sk, self.world)
-            lens, blob = ops.extract_words(text, sp)
+            blob = ops.gather_words(text, sp, offs, total_b)
             # per-partition blob byte counts: cumsum(lens) at boundaries
             bnd = torch.cumsum(counts_d, 0)
             if lens.numel():
@@ -668,6 +691,8 @@ class WordCountJob:
         else:
             fk, fv, fp = sk, sv, sp
             blob_src = text
+            cache = dict(packed=packed, offs=offs, total_bytes=total_b,
+                         cache_src=text)
 
         self._mark("shuffle_reduce")
         self._collect_timing()
@@ -678,4 +703,5 @@ class WordCountJob:
         return WordCountResult(
             keys=fk, counts=fv, pos=fp, blob_src=blob_src, nwords=nwords,
             hash_kind=("legacy-fnv" if legacy else
-                       "wordhash64" if dev.type == "cuda" else "fnv1a64"))
+                       "wordhash64" if dev.type == "cuda" else "fnv1a64"),
+            **(cache or {}))

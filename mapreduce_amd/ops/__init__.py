@@ -319,6 +319,94 @@ def extract_words(text: torch.Tensor, pos: torch.Tensor):
     return lens, blob
 
 
+def gather_words(text: torch.Tensor, pos: torch.Tensor, offs: torch.Tensor,
+                 total: int) -> torch.Tensor:
+    """The blob of extract_words for callers that already hold the
+    exclusive scan `offs` of the word lengths and its `total`: one gather,
+    no scan and no host sync."""
+    if not text.is_cuda:
+        from . import _cpu
+        return _cpu.extract_words(text, pos)[1]
+    if pos.numel() == 0:
+        return torch.empty(0, dtype=torch.uint8, device=text.device)
+    return ext().gather_bytes(text, pos, offs, int(total))
+
+
+# ---------------------------------------------------------------------------
+# table -> sorted, packed result (the word-count job's post-drain tail)
+# ---------------------------------------------------------------------------
+
+# caps of the extract_sorted kernels (ops/hip/extract_sorted.hip): keys one
+# wave ranks in LDS (a longer bin takes the composed path), lens per block
+# of the offsets scan
+EXTRACT_SORTED_RANK_M = 512
+EXTRACT_SORTED_SCAN_TILE = 2048
+
+
+def extract_sorted_caps():
+    """-> (RANK_M, SCAN_TILE): the extension's own values on a GPU machine,
+    the Python constants above on the CPU tier."""
+    if torch.cuda.is_available():
+        return tuple(int(c) for c in ext().extract_sorted_caps())
+    return EXTRACT_SORTED_RANK_M, EXTRACT_SORTED_SCAN_TILE
+
+
+def _extract_sorted_composed(table):
+    """extract_sorted through the general ops: extract + sort_by_key +
+    pos_len + cumsum.  The oracle of the native op, its fallback, and the
+    CPU tier."""
+    k, v, p = table.extract()
+    if p.numel():
+        sk, sv, sp = sort_by_key(k, v, p)
+    else:
+        sk, sv = sort_by_key(k, v)
+        sp = p
+    if sp.numel():
+        if sp.is_cuda:
+            lens = ext().pos_len(sp)
+        else:
+            lens = sp & 0xFFFF
+        offs = torch.cumsum(lens, 0) - lens
+        total = int((offs[-1] + lens[-1]).item())
+    else:
+        lens = offs = sp
+        total = 0
+    return sk, sv, sp, lens, offs, total, torch.cat([sk, sv, lens])
+
+
+def extract_sorted(table):
+    """-> (keys, counts, pos, lens, offs, total_bytes, packed): the table's
+    occupied slots in ascending u64 key order.  counts are the slots'
+    values, pos their exemplars, lens = pos & 0xFFFF, offs the exclusive
+    prefix sum of lens and total_bytes its end; packed is the contiguous
+    i64 buffer [keys | counts | lens] that keys, counts and lens view.
+    Without exemplar tracking pos, lens and offs are empty and total_bytes
+    is 0.
+
+    GPU tables below MR_EXTRACT_V2_MIN slots take the native op: a handful
+    of kernels and ONE host sync (the [n, total_bytes, overflow] readback).
+    A key set the rank kernel cannot hold (over EXTRACT_SORTED_RANK_M keys
+    sharing their top bits), larger tables, MR_EXTRACT_SORTED=0 and the
+    CPU tier compose the general ops instead, with identical results."""
+    import os
+    tkeys = getattr(table, "tkeys", None)
+    if (tkeys is None or not tkeys.is_cuda
+            or os.environ.get("MR_EXTRACT_SORTED", "1") == "0"
+            or table.cap >= int(os.environ.get("MR_EXTRACT_V2_MIN",
+                                               1 << 22))):
+        return _extract_sorted_composed(table)
+    packed, pos, offs, meta = ext().extract_sorted(table.tkeys, table.tvals,
+                                                   table.texm)
+    n, total, overflow = (int(x) for x in meta.tolist())
+    if overflow:
+        return _extract_sorted_composed(table)
+    has_pos = pos.numel() > 0
+    packed = packed[:(3 if has_pos else 2) * n]
+    return (packed[:n], packed[n:2 * n], pos[:n],
+            packed[2 * n:3 * n] if has_pos else pos[:0],
+            offs[:n], total, packed)
+
+
 # ---------------------------------------------------------------------------
 # lexicographic order of the dictionary (sorted-result guarantee, prefix
 # queries) — runs at the finalfn / serving boundary, never in the timed job

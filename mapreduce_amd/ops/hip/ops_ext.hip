@@ -14,6 +14,7 @@
 #include <mutex>
 #include <utility>
 
+#include "extract_sorted.hip"
 #include "gradsum.hip"
 #include "group.hip"
 #include "join.hip"
@@ -718,6 +719,72 @@ std::vector<torch::Tensor> hash_extract_v2(torch::Tensor tkeys,
                      ocap);
   return {okeys, ovals, opos, counter};
 }
+
+// Table -> (packed [keys | counts | lens] at stride n in a 3 * cap buffer,
+// pos, offs, meta = [n, total_bytes, overflow] on the HOST), keys ascending
+// in u64 order.  Seven launches (one zero fill + six kernels; five without
+// exemplars) and one readback, the meta copy, which is the op's only sync.
+// overflow != 0: some bin outgrew the rank kernel's LDS and its keys were
+// not written — the caller must take the general path instead.
+std::vector<torch::Tensor> extract_sorted(torch::Tensor tkeys,
+                                          torch::Tensor tvals,
+                                          torch::Tensor texm) {
+  check_dev_i64(tkeys, "tkeys");
+  check_dev_i64(tvals, "tvals");
+  if (texm.numel()) check_dev_i64(texm, "texm");
+  long cap = tkeys.numel();
+  TORCH_CHECK(cap > 0 && (cap & (cap - 1)) == 0,
+              "table capacity must be a power of 2");
+  TORCH_CHECK(cap < (1L << 31), "extract_sorted slots are u32: cap < 2^31");
+  TORCH_CHECK(tvals.numel() == cap &&
+                  (texm.numel() == 0 || texm.numel() == cap),
+              "tvals (and texm, when tracked) must match tkeys");
+  bool exm = texm.numel() > 0;
+  auto opts = tkeys.options();
+  auto o32 = opts.dtype(torch::kInt32);
+  long nbins = cap / XS_SLOTS_PER_BIN;
+  if (nbins < 1) nbins = 1;
+  int shift = 64;
+  for (long b = nbins; b > 1; b >>= 1) --shift;
+  long ntiles = (cap + XS_SCAN_TILE - 1) / XS_SCAN_TILE;
+  auto packed = torch::empty({3 * cap}, opts);
+  auto pos = torch::empty({exm ? cap : 0}, opts);
+  auto offs = torch::empty({exm ? cap : 0}, opts);
+  auto meta = torch::empty({3}, opts);
+  auto bins = torch::zeros({nbins}, o32);
+  auto bin_off = torch::empty({nbins + 1}, o32);
+  auto bkeys = torch::empty({cap}, opts);
+  auto bslot = torch::empty({cap}, o32);
+  auto tile_sums = torch::empty({ntiles}, opts);
+  u32* binp = reinterpret_cast<u32*>(bins.data_ptr<int>());
+  u32* offp = reinterpret_cast<u32*>(bin_off.data_ptr<int>());
+  u32* slotp = reinterpret_cast<u32*>(bslot.data_ptr<int>());
+  hipStream_t st = cur_stream();
+  hipLaunchKernelGGL(xs_hist_kernel, dim3(grid_for(cap)), dim3(XS_BLOCK), 0,
+                     st, u64cp(tkeys), cap, shift, binp);
+  hipLaunchKernelGGL(xs_bin_scan_kernel, dim3(1), dim3(XS_BINSCAN_BLOCK), 0,
+                     st, binp, (int)nbins, offp, meta.data_ptr<i64>());
+  hipLaunchKernelGGL(xs_scatter_kernel, dim3(grid_for(cap)), dim3(XS_BLOCK),
+                     0, st, u64cp(tkeys), cap, shift, binp, offp,
+                     u64p(bkeys), slotp);
+  hipLaunchKernelGGL(xs_rank_kernel,
+                     dim3((nbins + XS_WAVES - 1) / XS_WAVES), dim3(XS_BLOCK),
+                     0, st, u64cp(bkeys), slotp, offp, (int)nbins,
+                     tvals.data_ptr<i64>(), exm ? u64cp(texm) : nullptr,
+                     meta.data_ptr<i64>(), packed.data_ptr<i64>(),
+                     exm ? u64p(pos) : nullptr);
+  if (exm) {
+    hipLaunchKernelGGL(xs_tile_sums_kernel, dim3(ntiles), dim3(XS_BLOCK), 0,
+                       st, packed.data_ptr<i64>(), meta.data_ptr<i64>(),
+                       tile_sums.data_ptr<i64>());
+    hipLaunchKernelGGL(xs_offs_scan_kernel, dim3(ntiles), dim3(XS_BLOCK), 0,
+                       st, packed.data_ptr<i64>(), meta.data_ptr<i64>(),
+                       tile_sums.data_ptr<i64>(), offs.data_ptr<i64>());
+  }
+  return {packed, pos, offs, meta.cpu()};
+}
+
+std::vector<long> extract_sorted_caps() { return {XS_RANK_M, XS_SCAN_TILE}; }
 
 // ----------------------------------------------------------------------- K5b
 torch::Tensor head_flags(torch::Tensor keys) {
@@ -1572,6 +1639,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("hash_extract", &hash_extract);
   m.def("hash_extract_v2", &hash_extract_v2,
         "chunked compaction (HT_EMPTY-padded; mask/trim downstream)");
+  m.def("extract_sorted", &extract_sorted,
+        "table -> (packed keys|counts|lens, pos, offs, host meta), sorted");
+  m.def("extract_sorted_caps", &extract_sorted_caps,
+        "(RANK_M, SCAN_TILE) of extract_sorted");
   m.def("head_flags", &head_flags);
   m.def("seg_reduce_i64", &seg_reduce_i64);
   m.def("seg_reduce_i64_minmax", &seg_reduce_i64_minmax);
