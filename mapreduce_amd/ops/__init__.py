@@ -889,12 +889,14 @@ def _group_offsets(keys, flags):
     return keys.index_select(0, heads), offsets
 
 
-def _group_two_sort(keys, v, f64):
+def _group_two_sort(keys, v, f64, return_perm=False):
     """The composition: sort by order key, then stably by key."""
     ok = ext().group_order_keys(v, f64)
-    _, k1, v1 = sort_by_key(ok, keys, v)
-    _, v2 = sort_by_key(k1, v1)
-    return v2
+    cols = [keys, v]
+    if return_perm:  # -> (values, input rows)
+        cols.append(torch.arange(keys.numel(), device=keys.device))
+    cols = sort_by_key(*sort_by_key(ok, *cols)[1:])[1:]
+    return cols if return_perm else cols[0]
 
 
 def group_straddlers(offsets: torch.Tensor, tile: int):
@@ -911,13 +913,17 @@ def group_straddlers(offsets: torch.Tensor, tile: int):
 
 
 def sort_values_in_groups(keys_sorted: torch.Tensor, vals: torch.Tensor,
-                          offsets: Optional[torch.Tensor] = None):
+                          offsets: Optional[torch.Tensor] = None,
+                          return_perm: bool = False):
     """The value column ordered within every key: keys_sorted ascending in
     u64 bit order (the caller's contract), vals i64 or f64, one per key; the
     dtype is kept and the inputs are never written.  Order is that of
     group_order_keys; values with equal order keys keep their input order.
     offsets: what group_by_key_sorted returned for these keys, when the
-    caller holds it.
+    caller holds it.  return_perm=True: -> (sorted_vals, perm) with perm
+    i64[n] and sorted_vals == vals[perm] bit for bit; perm is the one stable
+    order on (key, order key of the value, input row), so a second column
+    can be carried through the ordering.
 
     Device path: every tile of GROUP_TILE rows is sorted in LDS by (segment,
     order key) — by rank counting where the tile's segments are at most
@@ -941,15 +947,18 @@ def sort_values_in_groups(keys_sorted: torch.Tensor, vals: torch.Tensor,
         if keys_sorted.dtype != torch.int64:
             raise TypeError("keys must be int64")
         from . import _cpu
-        return _cpu.sort_values_in_groups(keys_sorted, vals)
+        return _cpu.sort_values_in_groups(keys_sorted, vals, return_perm)
     import os
     keys = keys_sorted.contiguous()
     v = v.contiguous()
     if os.environ.get("MR_GROUP_TWO_SORT", "0") == "1":
+        if return_perm:
+            out, perm = _group_two_sort(keys, v, f64, True)
+            return out.view(vals.dtype), perm
         return _group_two_sort(keys, v, f64).view(vals.dtype)
     if n == 0:
         ext().group_tile_sort(keys, v, f64)  # the host checks still run
-        return vals.clone()
+        return (vals.clone(), v.clone()) if return_perm else vals.clone()
     e = ext()
     flags = e.head_flags(keys)
     seg = torch.cumsum(flags, 0)
@@ -957,8 +966,18 @@ def sort_values_in_groups(keys_sorted: torch.Tensor, vals: torch.Tensor,
         _, offsets = _group_offsets(keys, flags)
     tile = group_caps()[0]
     sidx, rows = group_straddlers(offsets, tile)
-    # all rows in straddlers: every slot is overwritten below
-    out = e.group_tile_sort(seg, v, f64) if rows < n else torch.empty_like(v)
+    # all rows in straddlers: every slot is overwritten below.  The tile
+    # pass writes out and perm at the same slots, and the straddlers' slots
+    # it leaves unwritten are overwritten in both columns
+    perm = None
+    if rows == n:
+        out = torch.empty_like(v)
+        if return_perm:
+            perm = torch.empty_like(v)
+    elif return_perm:
+        out, perm = e.group_tile_sort_perm(seg, v, f64)
+    else:
+        out = e.group_tile_sort(seg, v, f64)
     if rows:
         ns = sidx.numel()
         sst = offsets.index_select(0, sidx)
@@ -968,11 +987,16 @@ def sort_values_in_groups(keys_sorted: torch.Tensor, vals: torch.Tensor,
             torch.arange(ns, device=keys.device), slen, output_size=rows)
         ridx = (torch.arange(rows, device=keys.device)
                 + (sst - first).index_select(0, snum))
-        sv = v.index_select(0, ridx)
-        _, snum, sv = sort_by_key(e.group_order_keys(sv, f64), snum, sv)
-        _, sv = sort_by_key(snum, sv, bits=max(1, (ns - 1).bit_length()))
-        out.index_copy_(0, ridx, sv)
-    return out.view(vals.dtype)
+        # [straddler number, value(, input row)]
+        cols = [snum, v.index_select(0, ridx)] + ([ridx] if return_perm
+                                                  else [])
+        cols = sort_by_key(e.group_order_keys(cols[1], f64), *cols)[1:]
+        cols = sort_by_key(*cols, bits=max(1, (ns - 1).bit_length()))
+        out.index_copy_(0, ridx, cols[1])
+        if return_perm:
+            perm.index_copy_(0, ridx, cols[2])
+    out = out.view(vals.dtype)
+    return (out, perm) if return_perm else out
 
 
 def _group_rank_specs(fracs, interpolation: str):
@@ -1079,3 +1103,96 @@ def group_distinct(keys_sorted: torch.Tensor,
     each key; +0.0 and -0.0 count once, all NaNs count once."""
     flags = group_distinct_flags(keys_sorted, sorted_vals)
     return reduce_by_key_sorted(keys_sorted, flags, op="sum")[1]
+
+
+# ---------------------------------------------------------------------------
+# per-key running aggregates and sessions over grouped rows (K4/K5 for
+# reducers whose answer is as long as their input)
+# ---------------------------------------------------------------------------
+
+# caps of the scan kernels (ops/hip/seg_scan.hip): rows per tile, tiles per
+# loop trip of the one-block carry pass.  The CPU tier has no tiles; it
+# reports the same values so tests size their cases alike on both tiers.
+SEG_SCAN_TILE = 2048
+SEG_CARRY_CHUNK = 1024
+
+_SEG_SCAN_OPS = {"sum": 0, "min": 1, "max": 2}
+
+
+def seg_scan_caps():
+    """-> (SEG_SCAN_TILE, CARRY_CHUNK): the extension's own values on a GPU
+    machine, the Python constants above on the CPU tier."""
+    if torch.cuda.is_available():
+        return tuple(int(c) for c in ext().seg_scan_caps())
+    return SEG_SCAN_TILE, SEG_CARRY_CHUNK
+
+
+def scan_by_key_sorted(keys: torch.Tensor, vals: torch.Tensor,
+                       op: str = "sum") -> torch.Tensor:
+    """The running sum, minimum or maximum within each segment: row i holds
+    op over the rows of its segment up to and including i.  A row starts a
+    segment when it is row 0 or its key differs from the previous row's, so
+    keys need only be grouped, not sorted.  vals is i64 or f64, one per key;
+    the result has its dtype and length and the inputs are never written.
+
+    i64 sums wrap modulo 2^64.  f64 sums are IEEE in the kernel's own
+    association (tiles, waves, rounds of 64 rows; not left to right): exact
+    whenever every partial sum is representable.  min / max compare by
+    group_order_keys (-0.0 equals +0.0, NaN is the largest value) and keep
+    the stored bits of the earlier row among equal order keys.
+
+    Device path (ops/hip/seg_scan.hip): reduce-then-scan over tiles of
+    SEG_SCAN_TILE rows, three launches ordered by their boundaries alone,
+    no host sync, fewer than 2^31 rows."""
+    if op not in _SEG_SCAN_OPS:
+        raise ValueError(f"op must be 'sum', 'min' or 'max', got {op!r}")
+    v, f64 = _group_vals_i64(vals)
+    if not keys.is_cuda and not vals.is_cuda:
+        if keys.dtype != torch.int64:
+            raise TypeError("keys must be int64")
+        if vals.numel() != keys.numel():
+            raise ValueError("one value per key required")
+        _group_check_rows(keys.numel())
+        from . import _cpu
+        return _cpu.scan_by_key_sorted(keys, vals, op)
+    return ext().scan_by_key_sorted(keys, v, _SEG_SCAN_OPS[op],
+                                    f64).view(vals.dtype)
+
+
+def _session_gap(gap) -> int:
+    if isinstance(gap, bool) or not isinstance(gap, int):
+        raise TypeError(f"gap must be an int, got {gap!r}")
+    if not 0 <= gap < 2 ** 63:
+        raise ValueError(f"gap must be in [0, 2^63), got {gap}")
+    return gap
+
+
+def session_flags(keys_sorted: torch.Tensor, sorted_times: torch.Tensor,
+                  gap: int) -> torch.Tensor:
+    """flags i64[n]: 1 where a row starts a key, or where its time exceeds
+    the previous row's by more than gap.  Times are i64, ascending within
+    each key (f64 is refused); 0 <= gap < 2^63.  The difference is taken
+    between the order keys in u64 arithmetic and compared to gap as u64, so
+    it cannot overflow whatever the span.  No host sync."""
+    gap = _session_gap(gap)
+    if sorted_times.dtype != torch.int64:
+        raise TypeError(
+            f"session times must be int64, got {sorted_times.dtype}")
+    if not keys_sorted.is_cuda and not sorted_times.is_cuda:
+        if keys_sorted.dtype != torch.int64:
+            raise TypeError("keys must be int64")
+        if sorted_times.numel() != keys_sorted.numel():
+            raise ValueError("one time per key required")
+        _group_check_rows(keys_sorted.numel())
+        from . import _cpu
+        return _cpu.session_flags(keys_sorted, sorted_times, gap)
+    return ext().session_flags(keys_sorted, sorted_times, gap)
+
+
+def group_sessions(keys_sorted: torch.Tensor, sorted_times: torch.Tensor,
+                   gap: int):
+    """-> (skeys i64[nsess], soffsets i64[nsess + 1]): the key of every
+    session and the sessions' offsets into the rows; session s is rows
+    soffsets[s]:soffsets[s + 1].  One host sync (the session count)."""
+    flags = session_flags(keys_sorted, sorted_times, gap)
+    return _group_offsets(keys_sorted, flags)

@@ -390,11 +390,13 @@ def group_by_key_sorted(keys: torch.Tensor):
     return _from_u64(ku[heads]), torch.from_numpy(offsets)
 
 
-def sort_values_in_groups(keys: torch.Tensor, vals: torch.Tensor):
+def sort_values_in_groups(keys: torch.Tensor, vals: torch.Tensor,
+                          return_perm: bool = False):
     """np.lexsort (stable) on (key, order key): equal values keep their
     input order, as on the device."""
     order = np.lexsort((group_order_keys(vals), _u64(keys.contiguous())))
-    return vals[torch.from_numpy(order.astype(np.int64))]
+    perm = torch.from_numpy(order.astype(np.int64))
+    return (vals[perm], perm) if return_perm else vals[perm]
 
 
 def group_pick(offsets: torch.Tensor, vals: torch.Tensor, specs):
@@ -414,4 +416,46 @@ def group_distinct_flags(keys: torch.Tensor, vals: torch.Tensor):
     ok = group_order_keys(vals)
     flags = np.ones(len(ku), dtype=np.int64)
     flags[1:] = (ku[1:] != ku[:-1]) | (ok[1:] != ok[:-1])
+    return torch.from_numpy(flags)
+
+
+# ---- per-key running aggregates and sessions -------------------------------
+
+def scan_by_key_sorted(keys: torch.Tensor, vals: torch.Tensor, op: str):
+    """Inclusive scan within runs of equal keys, one run at a time: sums
+    left to right (i64 wrapping); min / max by order key, the earlier row's
+    bits kept among equal order keys."""
+    ku = _u64(keys.contiguous())
+    n = len(ku)
+    v = vals.contiguous()
+    out = torch.empty_like(v)
+    if n == 0:
+        return out
+    heads = np.flatnonzero(np.concatenate([[True], ku[1:] != ku[:-1]]))
+    ends = np.concatenate([heads[1:], [n]])
+    if op == "sum":
+        src = v.numpy() if v.dtype == torch.float64 else _u64(v)
+        dst = out.numpy() if v.dtype == torch.float64 else _u64(out)
+        with np.errstate(all="ignore"):
+            for a, b in zip(heads.tolist(), ends.tolist()):
+                np.cumsum(src[a:b], out=dst[a:b])
+        return out
+    ok = group_order_keys(v)
+    bits = _u64(v.view(torch.int64))
+    dst = _u64(out.view(torch.int64))
+    for a, b in zip(heads.tolist(), ends.tolist()):
+        g = ok[a:b]
+        best = (np.minimum if op == "min" else np.maximum).accumulate(g)
+        new = np.ones(b - a, dtype=bool)  # a strictly better row
+        new[1:] = g[1:] < best[:-1] if op == "min" else g[1:] > best[:-1]
+        src = np.maximum.accumulate(np.where(new, np.arange(b - a), 0))
+        dst[a:b] = bits[a:b][src]
+    return out
+
+
+def session_flags(keys: torch.Tensor, times: torch.Tensor, gap: int):
+    ku = _u64(keys.contiguous())
+    ok = group_order_keys(times)
+    flags = np.ones(len(ku), dtype=np.int64)
+    flags[1:] = (ku[1:] != ku[:-1]) | ((ok[1:] - ok[:-1]) > np.uint64(gap))
     return torch.from_numpy(flags)

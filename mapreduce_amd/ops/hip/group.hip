@@ -28,7 +28,9 @@
 // Every segment that lies wholly inside the tile is finished; a segment that
 // crosses a tile boundary is not (the host re-sorts those rows and
 // overwrites their slots; the rank pass does not write them at all).  A
-// tile that lies wholly inside one such segment is skipped.
+// tile that lies wholly inside one such segment is skipped.  The PERM
+// instantiation also stores the input row of every value it stores, at the
+// same index and under the same guards.
 //   LDS: 8 B + 4 B + 2 B per row = 28 KB at GROUP_TILE 2048, five blocks
 //   per CU.
 //
@@ -86,9 +88,11 @@ DEV bool group_less(u64 ka, u32 ma, u64 kb, u32 mb) {
   return ma < mb;
 }
 
+// PERM: also perm[output row] = the input row its value came from
+template <bool PERM>
 __global__ __launch_bounds__(GROUP_BLOCK) void group_tile_sort_kernel(
     const i64* __restrict__ seg, const u64* __restrict__ vals, long n,
-    int f64, u64* __restrict__ out) {
+    int f64, u64* __restrict__ out, i64* __restrict__ perm) {
   __shared__ u64 s_key[GROUP_TILE];
   __shared__ u32 s_meta[GROUP_TILE];
   __shared__ unsigned short s_start[GROUP_TILE + 1];
@@ -157,6 +161,7 @@ __global__ __launch_bounds__(GROUP_BLOCK) void group_tile_sort_kernel(
         r += (kj < ki || (kj == ki && j < i)) ? 1 : 0;
       }
       out[t0 + a + r] = vals[t0 + i];  // r <= b - a - 1: inside the tile
+      if (PERM) perm[t0 + a + r] = t0 + i;
     }
     return;
   }
@@ -182,7 +187,10 @@ __global__ __launch_bounds__(GROUP_BLOCK) void group_tile_sort_kernel(
 
   for (int i = tid; i < cnt; i += GROUP_BLOCK) {
     const int row = (int)(s_meta[i] & 0xFFFFu);
-    if (row < cnt) out[t0 + i] = vals[t0 + row];
+    if (row < cnt) {
+      out[t0 + i] = vals[t0 + row];
+      if (PERM) perm[t0 + i] = t0 + row;
+    }
   }
 }
 

@@ -23,6 +23,7 @@
 #include "postings_phrase.hip"
 #include "postings_query.hip"
 #include "radix_sort.hip"
+#include "seg_scan.hip"
 #include "token_ordinals.hip"
 
 namespace {
@@ -1489,12 +1490,36 @@ torch::Tensor group_tile_sort(torch::Tensor seg, torch::Tensor vals,
   auto out = torch::empty({n}, vals.options());
   if (n) {
     long ntiles = (n + GROUP_TILE - 1) / GROUP_TILE;
-    hipLaunchKernelGGL(group_tile_sort_kernel, dim3(ntiles),
+    hipLaunchKernelGGL(group_tile_sort_kernel<false>, dim3(ntiles),
                        dim3(GROUP_BLOCK), 0, cur_stream(),
                        seg.data_ptr<i64>(), u64cp(vals), n, (int)f64,
-                       u64p(out));
+                       u64p(out), (i64*)nullptr);
   }
   return out;
+}
+
+// group_tile_sort plus perm i64[n]: out[i] == vals[perm[i]] wherever out[i]
+// is specified; perm is unspecified exactly where out is.  No host sync.
+std::vector<torch::Tensor> group_tile_sort_perm(torch::Tensor seg,
+                                                torch::Tensor vals,
+                                                bool f64) {
+  check_dev_i64(seg, "seg");
+  check_dev_i64(vals, "vals");
+  TORCH_CHECK(seg.device() == vals.device(),
+              "seg and vals must be on the same device");
+  long n = vals.numel();
+  TORCH_CHECK(seg.numel() == n, "seg must hold one segment id per value");
+  check_group_rows(n);
+  auto out = torch::empty({n}, vals.options());
+  auto perm = torch::empty({n}, vals.options());
+  if (n) {
+    long ntiles = (n + GROUP_TILE - 1) / GROUP_TILE;
+    hipLaunchKernelGGL(group_tile_sort_kernel<true>, dim3(ntiles),
+                       dim3(GROUP_BLOCK), 0, cur_stream(),
+                       seg.data_ptr<i64>(), u64cp(vals), n, (int)f64,
+                       u64p(out), perm.data_ptr<i64>());
+  }
+  return {out, perm};
 }
 
 // out[s, q] = vals[off[s] + (num[q] * (len - 1) + add[q]) / den[q]], add =
@@ -1558,6 +1583,145 @@ torch::Tensor group_distinct_flags(torch::Tensor keys, torch::Tensor vals,
   return flags;
 }
 
+// ------------------------------------------------- per-key running aggregates
+// caps of the scan kernels: (rows per tile, tiles per trip of the carry pass)
+std::vector<long> seg_scan_caps() { return {SEG_SCAN_TILE, SEG_CARRY_CHUNK}; }
+
+namespace {
+void check_seg_rows(long n) {
+  TORCH_CHECK(n < (1L << 31), "scan ops take fewer than 2^31 rows, got ", n);
+}
+
+long check_seg_scan_cols(const torch::Tensor& keys,
+                         const torch::Tensor& vals, long op) {
+  check_dev_i64(keys, "keys");
+  check_dev_i64(vals, "vals");
+  TORCH_CHECK(keys.device() == vals.device(),
+              "keys and vals must be on the same device");
+  long n = keys.numel();
+  TORCH_CHECK(vals.numel() == n, "vals must hold one value per key");
+  check_seg_rows(n);
+  TORCH_CHECK(op >= SEG_SUM && op <= SEG_MAX,
+              "op must be 0 (sum), 1 (min) or 2 (max), got ", op);
+  return n;
+}
+
+void check_seg_tiles(const torch::Tensor& f, const torch::Tensor& a,
+                     const torch::Tensor& like, long ntiles,
+                     const char* what) {
+  check_dev_i64(f, what);
+  check_dev_i64(a, what);
+  TORCH_CHECK(f.device() == like.device() && a.device() == like.device(),
+              what, " must be on the device of the rows");
+  TORCH_CHECK(f.numel() == ntiles && a.numel() == ntiles, what,
+              " must hold one entry per tile (", ntiles, ")");
+}
+
+// one launch of KERNEL<op, f64> with the given grid
+#define SEG_SCAN_LAUNCH(KERNEL, grid, ...)                                  \
+  do {                                                                      \
+    dim3 g_(grid), b_(SEG_SCAN_BLOCK);                                      \
+    if (op == SEG_SUM && !f64)                                              \
+      hipLaunchKernelGGL((KERNEL<SEG_SUM, false>), g_, b_, 0, cur_stream(), \
+                         __VA_ARGS__);                                      \
+    else if (op == SEG_SUM)                                                 \
+      hipLaunchKernelGGL((KERNEL<SEG_SUM, true>), g_, b_, 0, cur_stream(),  \
+                         __VA_ARGS__);                                      \
+    else if (op == SEG_MIN && !f64)                                         \
+      hipLaunchKernelGGL((KERNEL<SEG_MIN, false>), g_, b_, 0, cur_stream(), \
+                         __VA_ARGS__);                                      \
+    else if (op == SEG_MIN)                                                 \
+      hipLaunchKernelGGL((KERNEL<SEG_MIN, true>), g_, b_, 0, cur_stream(),  \
+                         __VA_ARGS__);                                      \
+    else if (!f64)                                                          \
+      hipLaunchKernelGGL((KERNEL<SEG_MAX, false>), g_, b_, 0, cur_stream(), \
+                         __VA_ARGS__);                                      \
+    else                                                                    \
+      hipLaunchKernelGGL((KERNEL<SEG_MAX, true>), g_, b_, 0, cur_stream(),  \
+                         __VA_ARGS__);                                      \
+  } while (0)
+}  // namespace
+
+// Pass 1 of scan_by_key_sorted: (tile_f, tile_a) i64[ntiles], the head flag
+// bits and the aggregate behind the last head of every tile of
+// SEG_SCAN_TILE rows.  vals is the int64 view of an i64 or f64 column.
+std::vector<torch::Tensor> seg_scan_reduce(torch::Tensor keys,
+                                           torch::Tensor vals, long op,
+                                           bool f64) {
+  long n = check_seg_scan_cols(keys, vals, op);
+  long ntiles = (n + SEG_SCAN_TILE - 1) / SEG_SCAN_TILE;
+  auto tf = torch::empty({ntiles}, keys.options());
+  auto ta = torch::empty({ntiles}, keys.options());
+  if (ntiles)
+    SEG_SCAN_LAUNCH(seg_scan_reduce_kernel, ntiles, u64cp(keys), u64cp(vals),
+                    n, tf.data_ptr<i64>(), u64p(ta));
+  return {tf, ta};
+}
+
+// Pass 2: (carry_f, carry_a) i64[ntiles], the exclusive segmented scan of
+// the tile pairs, by one block.
+std::vector<torch::Tensor> seg_scan_carry(torch::Tensor tile_f,
+                                          torch::Tensor tile_a, long op,
+                                          bool f64) {
+  long ntiles = tile_f.numel();
+  check_seg_tiles(tile_f, tile_a, tile_f, ntiles, "tile_f and tile_a");
+  TORCH_CHECK(op >= SEG_SUM && op <= SEG_MAX,
+              "op must be 0 (sum), 1 (min) or 2 (max), got ", op);
+  auto cf = torch::empty({ntiles}, tile_f.options());
+  auto ca = torch::empty({ntiles}, tile_f.options());
+  if (ntiles)
+    SEG_SCAN_LAUNCH(seg_scan_carry_kernel, 1, tile_f.data_ptr<i64>(),
+                    u64cp(tile_a), ntiles, cf.data_ptr<i64>(), u64p(ca));
+  return {cf, ca};
+}
+
+// Pass 3: the running column, every tile rescanned behind its carry.
+torch::Tensor seg_scan_apply(torch::Tensor keys, torch::Tensor vals,
+                             torch::Tensor carry_f, torch::Tensor carry_a,
+                             long op, bool f64) {
+  long n = check_seg_scan_cols(keys, vals, op);
+  long ntiles = (n + SEG_SCAN_TILE - 1) / SEG_SCAN_TILE;
+  check_seg_tiles(carry_f, carry_a, keys, ntiles, "carry_f and carry_a");
+  auto out = torch::empty({n}, vals.options());
+  if (ntiles)
+    SEG_SCAN_LAUNCH(seg_scan_apply_kernel, ntiles, u64cp(keys), u64cp(vals),
+                    n, carry_f.data_ptr<i64>(), u64cp(carry_a), u64p(out));
+  return out;
+}
+
+// running[i] = op over the rows of i's segment up to and including i; a
+// segment starts at row 0 and wherever the key changes.  Three launches, no
+// host sync; the inputs are never written.
+torch::Tensor scan_by_key_sorted(torch::Tensor keys, torch::Tensor vals,
+                                 long op, bool f64) {
+  long n = check_seg_scan_cols(keys, vals, op);
+  if (!n) return torch::empty({0}, vals.options());
+  auto t = seg_scan_reduce(keys, vals, op, f64);
+  auto c = seg_scan_carry(t[0], t[1], op, f64);
+  return seg_scan_apply(keys, vals, c[0], c[1], op, f64);
+}
+
+// flags i64[n]: 1 where a row starts a key or its i64 time exceeds the
+// previous row's by more than gap (times ascending within each key).  No
+// host sync.
+torch::Tensor session_flags(torch::Tensor keys, torch::Tensor times,
+                            long gap) {
+  check_dev_i64(keys, "keys");
+  check_dev_i64(times, "times");
+  TORCH_CHECK(keys.device() == times.device(),
+              "keys and times must be on the same device");
+  long n = keys.numel();
+  TORCH_CHECK(times.numel() == n, "times must hold one time per key");
+  check_seg_rows(n);
+  TORCH_CHECK(gap >= 0, "gap must be in [0, 2^63), got ", gap);
+  auto flags = torch::empty({n}, keys.options());
+  if (n)
+    hipLaunchKernelGGL(seg_session_flags_kernel, dim3(grid_for(n)),
+                       dim3(SEG_SCAN_BLOCK), 0, cur_stream(), u64cp(keys),
+                       u64cp(times), n, (u64)gap, flags.data_ptr<i64>());
+  return flags;
+}
+
 // Occupancy of the default word-count tokenizer instantiation on the
 // current device, as the runtime sees it (blocks/CU clips the grid; the
 // register count and static LDS are what decide it).
@@ -1582,6 +1746,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "u64 order key of each i64 / f64 value");
   m.def("group_tile_sort", &group_tile_sort,
         "values ordered inside every segment that fits one tile");
+  m.def("group_tile_sort_perm", &group_tile_sort_perm,
+        "group_tile_sort plus the input row of every value");
+  m.def("seg_scan_caps", &seg_scan_caps,
+        "(TILE, CARRY_CHUNK) of the segmented scan");
+  m.def("scan_by_key_sorted", &scan_by_key_sorted,
+        "inclusive sum/min/max scan within runs of equal keys");
+  m.def("seg_scan_reduce", &seg_scan_reduce,
+        "pass 1 of scan_by_key_sorted: per-tile (flags, aggregate)");
+  m.def("seg_scan_carry", &seg_scan_carry,
+        "pass 2 of scan_by_key_sorted: per-tile carry-in");
+  m.def("seg_scan_apply", &seg_scan_apply,
+        "pass 3 of scan_by_key_sorted: the running column");
+  m.def("session_flags", &session_flags,
+        "1 where a row starts a key or follows a gap in time");
   m.def("group_pick", &group_pick,
         "values at exact rank fractions of each ordered segment");
   m.def("group_distinct_flags", &group_distinct_flags,

@@ -86,8 +86,10 @@ class Server:
         self.stall_timeout = params.get("stall_timeout", 600.0)
         self.verbose = params.get("verbose", True)
         self.fns = FnSet(fns, self.params["init_args"])
-        # a malformed "group" family reducer is refused here, not mid-task
+        # a malformed "group" or "window" family reducer is refused here,
+        # not mid-task
         self.parse_group_reducer(self.fns.reducefn_gpu)
+        self.parse_window_reducer(self.fns.reducefn_gpu)
         self.fs = fsmod.router(storage, self.params["path"])
         return self
 
@@ -152,10 +154,38 @@ class Server:
             raise bad
         return op, fracs
 
+    # per-key running aggregates and sessions: reducers over the ordered
+    # rows of a key whose answer is as long as their input
+    GPU_WINDOW_REDUCERS = {"cumsum": "sum", "cummin": "min", "cummax": "max",
+                           "sessions": None}
+
+    @classmethod
+    def parse_window_reducer(cls, name):
+        """reducefn_gpu of the "window" family -> (op, parameter), or None
+        when the name belongs to another family.  "cumsum", "cummin" and
+        "cummax" take no parameter; "sessions:GAP" gives GAP, a decimal
+        integer with 0 <= GAP < 2^63.  A malformed name raises ValueError
+        naming the string."""
+        if not isinstance(name, str):
+            return None
+        op, sep, arg = name.partition(":")
+        if op not in cls.GPU_WINDOW_REDUCERS:
+            return None
+        bad = ValueError(
+            f"malformed reducefn_gpu {name!r}: expected 'cumsum', 'cummin', "
+            "'cummax' or 'sessions:GAP' with a decimal 0 <= GAP < 2^63")
+        if op != "sessions":
+            if sep:
+                raise bad
+            return op, None
+        if not (arg.isascii() and arg.isdigit() and int(arg) < 2 ** 63):
+            raise bad
+        return op, int(arg)
+
     def _gpu_engine_kind(self) -> Optional[str]:
         """Which GPU engine family this task routes to, or None.
 
-        Seven families (one worked example each; README table):
+        Eight families (one worked example each; README table):
           "bytes"   mapfn_gpu + reducefn_gpu="sum" — fused tokenize/
                     combine wordcount engine (examples/wordcount)
           "pairs"   mapfn_gpu_pairs + sum/min/max/minmax — keyed
@@ -171,6 +201,9 @@ class Server:
           "group"   mapfn_gpu_pairs + group/median/quantile:N/D,.../
                     topk:K/bottomk:K/distinct — per-key order statistics
                     over the whole value list (examples/percentiles)
+          "window"  mapfn_gpu_pairs + cumsum/cummin/cummax/sessions:GAP —
+                    per-key running aggregates and sessions over the
+                    ordered rows (examples/sessions)
 
         MR_GPU_TIER=off forces host tier; =force routes the GPU data
         path onto the CPU-ops engine (testing without a GPU)."""
@@ -213,6 +246,11 @@ class Server:
             # reducers over the whole value list of a key: not
             # associative, so there are no property flags to require
             kind = "group"
+        elif (callable(fns.mapfn_gpu_pairs)
+              and self.parse_window_reducer(fns.reducefn_gpu) is not None):
+            # running aggregates and sessions depend on the order of a
+            # key's rows: not associative either, no property flags
+            kind = "window"
         elif (callable(fns.mapfn_gpu_pairs)
               and fns.reducefn_gpu in self.GPU_PAIR_REDUCERS
               and fns.associative and fns.commutative
@@ -895,6 +933,128 @@ class Server:
         })
         self.print_stats()
 
+    def _loop_gpu_window(self) -> None:
+        """Running-aggregate GPU engine: the task's emitted rows are staged
+        as device columns (mapfn_gpu_pairs), grouped by key with the rows of
+        every key in order (gpu/window.py: sort, mulhi-partitioned
+        all-to-all, ops.sort_values_in_groups with the row permutation) and
+        reduced by reducefn_gpu:
+
+          "cumsum" / "cummin" / "cummax"
+              mapfn_gpu_pairs returns (keys, order, vals); finalfn receives
+              (key, [(order, running), ...]), the rows ascending by
+              (order, value) and running = the sum / min / max of the
+              values up to and including the row (ops.scan_by_key_sorted)
+          "sessions:GAP"
+              mapfn_gpu_pairs returns (keys, times); finalfn receives
+              (key, [(start, end, count), ...]), one triple per session: a
+              row opens a session when it starts its key or its time
+              exceeds the previous one by more than GAP
+
+        finalfn receives the pairs in global u64 key order: rank r owns the
+        r-th contiguous range of the key space.
+
+        Contract: int64-representable keys; floats stage as f64 and ints as
+        i64, uniformly across ranks; session times are integers."""
+        import torch
+
+        from .gpu import dist as dx
+        from .gpu.window import WindowJob
+
+        t_start = gettime()
+        rank, world = dx.world_info()
+        device = (torch.device("cuda", torch.cuda.current_device())
+                  if torch.cuda.is_available() else torch.device("cpu"))
+        name = self.fns.reducefn_gpu
+        op, arg = self.parse_window_reducer(name)
+        ncols = 2 if op == "sessions" else 3
+        what = ("(keys, times)" if op == "sessions"
+                else "(keys, order, vals)")
+        decode = self.fns.gpu_key_decode or (lambda k: k)
+        gtask = Task(self.coord, key="task_gpu")
+        staged = None  # (job signature, columns) — iteration reuse
+
+        def stage(col):
+            # floats stage as f64 from the start: as_tensor's default
+            # (f32) would round them before the widening; an empty list
+            # is f32 to torch and decides nothing
+            t = torch.as_tensor(col)
+            if t.is_floating_point() and t.numel():
+                return torch.as_tensor(col, dtype=torch.float64)
+            return t.to(torch.int64)
+
+        while not self.finished:
+            if rank == 0:
+                gtask.create_collection(TASK_STATUS.WAIT, {
+                    "fns": {"engine": f"window:{op}"},
+                    "storage": "hbm", "result_ns": "result",
+                }, self.iteration)
+            jobs = self._collect_taskfn_jobs()
+            mine = [kv for i, kv in enumerate(jobs) if i % world == rank]
+            if rank == 0:
+                gtask.set_task_status(TASK_STATUS.MAP)
+            sig = [k for k, _ in mine]
+            if staged is None or staged[0] != sig:
+                parts = [[] for _ in range(ncols)]
+                for k, v in mine:
+                    out = self.fns.mapfn_gpu_pairs(k, v)
+                    if not (isinstance(out, (tuple, list))
+                            and len(out) == ncols):
+                        raise ValueError(
+                            f"mapfn_gpu_pairs must return {what} under "
+                            f"reducefn_gpu={name!r}; job {k!r} returned "
+                            + (f"a {len(out)}-tuple"
+                               if isinstance(out, (tuple, list))
+                               else type(out).__name__))
+                    parts[0].append(torch.as_tensor(out[0],
+                                                    dtype=torch.int64))
+                    for c in range(1, ncols):
+                        parts[c].append(stage(out[c]))
+                # a rank may stage nothing yet receive rows in the
+                # shuffle: the ranks agree on each column's dtype
+                isf = torch.tensor(
+                    [int(any(t.is_floating_point() for t in parts[c]))
+                     for c in range(ncols)], dtype=torch.int64,
+                    device=device)
+                if world > 1:
+                    import torch.distributed as td
+                    td.all_reduce(isf, op=td.ReduceOp.MAX)
+                cols = []
+                for c, f in enumerate(isf.cpu().tolist()):
+                    dt = torch.float64 if f else torch.int64
+                    cols.append(torch.cat(parts[c]).to(dt).to(device)
+                                if parts[c]
+                                else torch.empty(0, dtype=dt, device=device))
+                staged = (sig, cols)
+            cols = staged[1]
+            if rank == 0:
+                gtask.set_task_status(TASK_STATUS.REDUCE)
+            res = WindowJob(device).run(*cols)
+            if op == "sessions":
+                host = res.sessions(arg).to_host()
+            else:
+                run = res.scan(self.GPU_WINDOW_REDUCERS[op]).cpu().tolist()
+                off = res.offsets.cpu().tolist()
+                rows = list(zip(res.order.cpu().tolist(), run))
+                host = [(k, rows[off[s]:off[s + 1]])
+                        for s, k in enumerate(res.keys.cpu().tolist())]
+            pairs = [(decode(int(k)), rows) for k, rows in host]
+            if rank == 0:
+                gtask.set_task_status(TASK_STATUS.FINISHED)
+            # rank-major concatenation IS global key order: no re-sort
+            reply = self._gpu_finalize_round(pairs, rank, world)
+            if reply == "loop":
+                self.iteration += 1
+                self._log(f"iterative loop -> iteration {self.iteration}")
+            else:
+                self.finished = True
+        self.stats.update({
+            "tier": "gpu", "engine": f"window:{op}",
+            "map_failed": 0, "reduce_failed": 0,
+            "total_time": gettime() - t_start,
+        })
+        self.print_stats()
+
     # ------------------------------------------------------------ map phase
     def _prepare_map(self) -> None:
         """server_prepare_map (server.lua:249-276): run taskfn(emit), check
@@ -1076,6 +1236,7 @@ class Server:
                   "sort": self._loop_gpu_sort,
                   "join": self._loop_gpu_join,
                   "group": self._loop_gpu_group,
+                  "window": self._loop_gpu_window,
                   "index": self._loop_gpu_index,
                   "gradsum": self._loop_gpu_grads}[kind]
             try:
