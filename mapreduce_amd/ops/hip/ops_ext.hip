@@ -92,8 +92,13 @@ long tok_grid(K kfn, int blockn, long n, long tile_bytes) {
   return blocks < kMaxBlocks ? blocks : kMaxBlocks;
 }
 
-// LDS-staged scatter (v2) is the default — direct scatter (v1) measured
+// LDS-staged scatter is the default — direct scatter (v1) measured
 // ~2.5x slower on write coalescing; MR_RADIX_V1=1 switches back for A/B.
+// The staged scatter ranks once from registers (v3, radix_sort.hip);
+// MR_RADIX_V2=1 selects its predecessor with the per-round block barriers
+// (v2, same output bit for bit), and the bucketize histogram that went
+// with it, for A/B inside one session.  Both switches are read once per
+// process.
 // MR_RS_ITEMS ∈ {4, 8}: radix tile = 256*ITEMS.  8 = longer digit runs
 // (better write coalescing), 4 = half the LDS stage (38->22 KB, 4->7
 // blocks/CU).  v1 (direct scatter) stays ITEMS=8.
@@ -114,6 +119,28 @@ bool radix_v1_forced() {
   return v && v[0] == '1';
 }
 
+bool radix_v2_forced() {
+  static int f = -1;
+  if (f < 0) {
+    const char* v = getenv("MR_RADIX_V2");
+    f = (v && v[0] == '1') ? 1 : 0;
+  }
+  return f == 1;
+}
+
+// the staged scatter this process runs, for one set of template arguments.
+// LATE (v3 only) = fetch the payload at staging time instead of up front:
+// faster for the full sorts (TeraSort's 671M-record passes: 8.7 against
+// 10.4 ms, v2 9.4), while the spill drain's bucketize, which shares the chip
+// with the next job's tokenizer, steps faster with everything in flight at
+// once (profiles/scatter_rank_r06.md).
+#define RS_STAGED_SCATTER(VT, SKIP, BT, LATE)                              \
+  (radix_v2_forced()                                                       \
+       ? (rs_items() == 4 ? radix_scatter_v2_kernel<4, VT, SKIP, BT>       \
+                          : radix_scatter_v2_kernel<8, VT, SKIP, BT>)      \
+       : (rs_items() == 4 ? radix_scatter_v3_kernel<4, VT, SKIP, BT, LATE> \
+                          : radix_scatter_v3_kernel<8, VT, SKIP, BT, LATE>))
+
 void launch_radix_hist(const u64* kin, long n, int shift, long ntiles,
                        i64* hist) {
   auto kfn = rs_items() == 4 ? radix_hist_kernel<4> : radix_hist_kernel<8>;
@@ -131,8 +158,7 @@ void launch_radix_scatter(const u64* kin, const u64* vin, long n, int shift,
                        cur_stream(), kin, vin, n, shift, ntiles, base, kout,
                        vout);
   else {
-    auto kfn = rs_items() == 4 ? radix_scatter_v2_kernel<4>
-                               : radix_scatter_v2_kernel<8>;
+    auto kfn = RS_STAGED_SCATTER(u64, false, i64, true);
     hipLaunchKernelGGL(kfn, dim3(ntiles), dim3(RS_BLOCK),
                        0, cur_stream(), kin, vin, n, shift, ntiles, base,
                        kout, vout);
@@ -142,8 +168,7 @@ void launch_radix_scatter(const u64* kin, const u64* vin, long n, int shift,
 void launch_radix_scatter32(const u64* kin, const u32* vin, long n,
                             int shift, long ntiles, const i64* base,
                             u64* kout, u32* vout) {
-  auto kfn = rs_items() == 4 ? radix_scatter_v2_kernel<4, u32>
-                             : radix_scatter_v2_kernel<8, u32>;
+  auto kfn = RS_STAGED_SCATTER(u32, false, i64, true);
   hipLaunchKernelGGL(kfn, dim3(ntiles), dim3(RS_BLOCK), 0, cur_stream(),
                      kin, vin, n, shift, ntiles, base, kout, vout);
 }
@@ -154,8 +179,13 @@ void launch_radix_scatter32(const u64* kin, const u32* vin, long n,
 template <bool SKIP>
 void launch_bucketize_hist(const u64* kin, long n, int shift, long ntiles,
                            u32* hist) {
-  auto kfn = rs_items() == 4 ? radix_hist_kernel<4, SKIP, u32>
-                             : radix_hist_kernel<8, SKIP, u32>;
+  // wide loads (WIDE): measured on this histogram only, 46 -> 40 us per
+  // job; MR_RADIX_V2=1 brings the narrow form back with the old scatter
+  auto kfn = rs_items() == 4 ? radix_hist_kernel<4, SKIP, u32, true>
+                             : radix_hist_kernel<8, SKIP, u32, true>;
+  if (radix_v2_forced())
+    kfn = rs_items() == 4 ? radix_hist_kernel<4, SKIP, u32>
+                          : radix_hist_kernel<8, SKIP, u32>;
   hipLaunchKernelGGL(kfn, dim3(ntiles), dim3(RS_BLOCK), 0, cur_stream(),
                      kin, n, shift, ntiles, hist);
 }
@@ -164,8 +194,7 @@ template <typename VT, bool SKIP>
 void launch_bucketize_scatter(const u64* kin, const VT* vin, long n,
                               int shift, long ntiles, const u32* base,
                               u64* kout, VT* vout) {
-  auto kfn = rs_items() == 4 ? radix_scatter_v2_kernel<4, VT, SKIP, u32>
-                             : radix_scatter_v2_kernel<8, VT, SKIP, u32>;
+  auto kfn = RS_STAGED_SCATTER(VT, SKIP, u32, false);
   hipLaunchKernelGGL(kfn, dim3(ntiles), dim3(RS_BLOCK), 0, cur_stream(),
                      kin, vin, n, shift, ntiles, base, kout, vout);
 }

@@ -34,9 +34,12 @@
 template <bool SKIP>
 DEV bool rs_live(u64 k) { return !SKIP || k != HT_EMPTY; }
 
+// WIDE: a full, 16-byte-aligned tile is read two keys per load with all of
+// a thread's loads issued before its first LDS atomic (which keys a thread
+// counts does not matter to a histogram).
 // HT: histogram entry type.  i64 feeds the torch cumsum of the full sort;
 // u32 (a tile holds <= 2048 records) feeds the native bucketize scan.
-template <int ITEMS, bool SKIP = false, typename HT = i64>
+template <int ITEMS, bool SKIP = false, typename HT = i64, bool WIDE = false>
 __global__ __launch_bounds__(RS_BLOCK) void radix_hist_kernel(
     const u64* __restrict__ keys, long n, int shift, long ntiles,
     HT* __restrict__ hist) {
@@ -45,11 +48,28 @@ __global__ __launch_bounds__(RS_BLOCK) void radix_hist_kernel(
   __syncthreads();
   long tile = blockIdx.x;
   long base = tile * (RS_BLOCK * ITEMS);
-  for (int r = 0; r < ITEMS; ++r) {
-    long i = base + r * RS_BLOCK + threadIdx.x;
-    if (i < n) {
-      u64 k = keys[i];
-      if (rs_live<SKIP>(k)) atomicAdd(&lh[(u32)((k >> shift) & 0xFF)], 1u);
+  if (WIDE && base + RS_BLOCK * ITEMS <= n &&
+      ((unsigned long long)keys & 15) == 0) {
+    // full tile, 16-byte aligned: two keys per load, every load of the
+    // thread issued before the first LDS atomic
+    const ulonglong2* p = reinterpret_cast<const ulonglong2*>(keys + base);
+    ulonglong2 q[ITEMS / 2];
+    #pragma unroll
+    for (int j = 0; j < ITEMS / 2; ++j) q[j] = p[j * RS_BLOCK + threadIdx.x];
+    #pragma unroll
+    for (int j = 0; j < ITEMS / 2; ++j) {
+      if (rs_live<SKIP>(q[j].x))
+        atomicAdd(&lh[(u32)((q[j].x >> shift) & 0xFF)], 1u);
+      if (rs_live<SKIP>(q[j].y))
+        atomicAdd(&lh[(u32)((q[j].y >> shift) & 0xFF)], 1u);
+    }
+  } else {
+    for (int r = 0; r < ITEMS; ++r) {
+      long i = base + r * RS_BLOCK + threadIdx.x;
+      if (i < n) {
+        u64 k = keys[i];
+        if (rs_live<SKIP>(k)) atomicAdd(&lh[(u32)((k >> shift) & 0xFF)], 1u);
+      }
     }
   }
   __syncthreads();
@@ -172,6 +192,185 @@ __global__ __launch_bounds__(RS_BLOCK) void radix_scatter_v2_kernel(
   }
 }
 
+DEV u32 wave_incl_scan_u32(u32 v, int lane) {
+  #pragma unroll
+  for (int off = 1; off < WAVE; off <<= 1) {
+    u32 o = __shfl_up(v, off, WAVE);
+    if (lane >= off) v += o;
+  }
+  return v;
+}
+
+// v3: the v2 scatter with the ranking's waits taken out — same arguments,
+// same (bit-identical, stable) output, default since MR_RADIX_V2=1 became
+// the A/B switch.  Per tile:
+//   1. blocked mapping, loaded once: wave w, round r, lane l owns tile index
+//      (w*ITEMS + r)*64 + l, so (wave, round, lane) order IS index order.
+//      All ITEMS keys go to registers up front with every load in flight,
+//      so no load latency is left inside the ranking.  The payload comes
+//      with them, or (LATE) is fetched at staging time by the lanes that
+//      stage a record; which is faster depends on the caller (ops_ext.hip).
+//   2. wave-private ranking, no block barrier: wcnt[wave][d] carries the
+//      digit-d count of this wave's EARLIER rounds; a lane's in-wave rank is
+//      that plus popc(same-digit lanes below it); the group's leader then
+//      adds the group size.  Rounds depend on each other only through one
+//      wave's own LDS row, ordered by a wavefront-scope fence.
+//   3. one cross-wave pass: thread b turns wcnt[0..3][b] into exclusive
+//      wave bases and the digit total (= the tile histogram; no separate
+//      histogram phase, no second key read), a 256-thread wave scan + four
+//      wave sums gives digit_start, which is folded straight into
+//      wcnt[w][b] = digit_start[b] + wavebase[w][b] and
+//      gbase[b] = base[b][tile] - digit_start[b] (base loaded at entry).
+//   4. stage at wcnt[wave][d] + rank, barrier, stream out to gbase[d] + s.
+// LDS: wcnt + gbase + the two stages — v2's footprint minus cnt_base and
+// digit_start (the four wave sums borrow stage_k[0..3], which is not
+// written before the barrier that follows their last read).
+template <int ITEMS, typename VT = u64, bool SKIP = false, typename BT = i64,
+          bool LATE = false>
+__global__ __launch_bounds__(RS_BLOCK) void radix_scatter_v3_kernel(
+    const u64* __restrict__ keys, const VT* __restrict__ vals, long n,
+    int shift, long ntiles, const BT* __restrict__ base_dx,
+    u64* __restrict__ okeys, VT* __restrict__ ovals) {
+  static_assert(RS_BLOCK == RS_BINS, "thread b owns digit b");
+  __shared__ u32 wcnt[RS_WAVES][RS_BINS];
+  __shared__ BT gbase[RS_BINS];
+  __shared__ u64 stage_k[(RS_BLOCK * ITEMS)];
+  __shared__ VT stage_v[(RS_BLOCK * ITEMS)];
+  long tile = blockIdx.x;
+  long tbase = tile * (RS_BLOCK * ITEMS);
+  long tile_n = n - tbase < (RS_BLOCK * ITEMS) ? n - tbase : (RS_BLOCK * ITEMS);
+  int wave = threadIdx.x / WAVE;
+  int lane = threadIdx.x % WAVE;
+  u64 lt_mask = ((u64)1 << lane) - 1;
+  bool has_vals = ovals != nullptr;
+
+  // ---- everything this thread reads from global memory, issued at once.
+  // Loads past the end re-read the last record instead of being
+  // predicated: a "load or keep the register" select makes the compiler
+  // branch around each load and wait for the earlier ones first.
+  BT my_base = base_dx[(long)threadIdx.x * ntiles + tile];
+  long i0 = tbase + (long)(wave * ITEMS) * WAVE + lane;
+  u64 k[ITEMS];
+  VT v[ITEMS];
+  bool valid[ITEMS];
+  #pragma unroll
+  for (int r = 0; r < ITEMS; ++r) {
+    long i = i0 + (long)r * WAVE;
+    k[r] = keys[i < n ? i : n - 1];
+  }
+  if (has_vals && !LATE) {
+    // a pad's payload is fetched and dropped rather than making every
+    // payload load wait for its key
+    #pragma unroll
+    for (int r = 0; r < ITEMS; ++r) {
+      long i = i0 + (long)r * WAVE;
+      v[r] = vals[i < n ? i : n - 1];
+    }
+  } else {
+    #pragma unroll
+    for (int r = 0; r < ITEMS; ++r) v[r] = 0;
+  }
+  #pragma unroll
+  for (int r = 0; r < ITEMS; ++r)
+    valid[r] = i0 + (long)r * WAVE < n && rs_live<SKIP>(k[r]);
+
+  // ---- wave-private stable ranks (this wave's wcnt row only)
+  #pragma unroll
+  for (int b = lane; b < RS_BINS; b += WAVE) wcnt[wave][b] = 0;
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  u32 rank[ITEMS];
+  #pragma unroll
+  for (int r = 0; r < ITEMS; ++r) {
+    u32 d = valid[r] ? (u32)((k[r] >> shift) & 0xFF) : 0;
+    u64 m = __ballot(valid[r]);
+    #pragma unroll
+    for (int b = 0; b < 8; ++b) {
+      u64 bb = __ballot(valid[r] && ((d >> b) & 1));
+      m &= ((d >> b) & 1) ? bb : ~bb;
+    }
+    u32 prev = valid[r] ? wcnt[wave][d] : 0;
+    rank[r] = prev + (u32)__popcll(m & lt_mask);
+    // every lane's read of this round precedes the leaders' updates ...
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    if (valid[r] && lane == __ffsll((unsigned long long)m) - 1)
+      wcnt[wave][d] = prev + (u32)__popcll(m);
+    // ... which precede every lane's read of the next round
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
+  __syncthreads();
+
+  // ---- one cross-wave pass: thread b owns digit b
+  u32 wb[RS_WAVES];
+  u32 total = 0;
+  #pragma unroll
+  for (int w = 0; w < RS_WAVES; ++w) {
+    wb[w] = total;
+    total += wcnt[w][threadIdx.x];
+  }
+  u32 incl = wave_incl_scan_u32(total, lane);
+  if (lane == WAVE - 1) stage_k[wave] = incl;  // wave sums, see header
+  __syncthreads();
+  u32 pre = 0, all = 0;
+  #pragma unroll
+  for (int w = 0; w < RS_WAVES; ++w) {
+    u32 ws = (u32)stage_k[w];
+    if (w < wave) pre += ws;
+    all += ws;
+  }
+  u32 dstart = pre + incl - total;  // digit_start[b]
+  #pragma unroll
+  for (int w = 0; w < RS_WAVES; ++w) wcnt[w][threadIdx.x] = dstart + wb[w];
+  gbase[threadIdx.x] = my_base - (BT)dstart;  // u32: wraps, undone at use
+  __syncthreads();
+
+  // ---- stage in (digit, stable rank) order: all slot reads, then all
+  // writes, so the LDS latencies overlap instead of queueing per record
+  #pragma unroll
+  for (int r = 0; r < ITEMS; ++r) {
+    u32 d = (u32)((k[r] >> shift) & 0xFF);
+    rank[r] += valid[r] ? wcnt[wave][d] : 0;  // now the stage slot
+  }
+  #pragma unroll
+  for (int r = 0; r < ITEMS; ++r) {
+    if (valid[r]) {
+      stage_k[rank[r]] = k[r];
+      if (has_vals)
+        stage_v[rank[r]] = LATE ? vals[i0 + (long)r * WAVE] : v[r];
+    }
+  }
+  __syncthreads();
+
+  // ---- stream out in stage order: coalesced within each digit run.
+  // SKIP staged only the live records (`all` of them): slots past that
+  // were never written and are not read.  Same batching: keys and
+  // payloads, then bases, then the stores.
+  u32 nstage = SKIP ? all : (u32)tile_n;
+  long pos[ITEMS];
+  #pragma unroll
+  for (int j = 0; j < ITEMS; ++j) {
+    u32 s = j * RS_BLOCK + threadIdx.x;
+    k[j] = s < nstage ? stage_k[s] : 0;
+    if (has_vals) v[j] = s < nstage ? stage_v[s] : (VT)0;
+  }
+  #pragma unroll
+  for (int j = 0; j < ITEMS; ++j) {
+    u32 s = j * RS_BLOCK + threadIdx.x;
+    u32 d = (u32)((k[j] >> shift) & 0xFF);
+    pos[j] = (long)(BT)(gbase[d] + (BT)s);
+  }
+  #pragma unroll
+  for (int j = 0; j < ITEMS; ++j) {
+    u32 s = j * RS_BLOCK + threadIdx.x;
+    if (s < nstage) {
+      okeys[pos[j]] = k[j];
+      if (has_vals) ovals[pos[j]] = v[j];
+    }
+  }
+}
+
 __global__ __launch_bounds__(RS_BLOCK) void radix_scatter_kernel(
     const u64* __restrict__ keys, const u64* __restrict__ vals, long n,
     int shift, long ntiles, const i64* __restrict__ base_dx,
@@ -248,15 +447,6 @@ __global__ __launch_bounds__(RS_BLOCK) void radix_scatter_kernel(
 //      n < 2^32).
 // ---------------------------------------------------------------------------
 #define RS_SCAN_UNROLL 4
-
-DEV u32 wave_incl_scan_u32(u32 v, int lane) {
-  #pragma unroll
-  for (int off = 1; off < WAVE; off <<= 1) {
-    u32 o = __shfl_up(v, off, WAVE);
-    if (lane >= off) v += o;
-  }
-  return v;
-}
 
 __global__ __launch_bounds__(RS_BLOCK) void rs_row_totals_kernel(
     const u32* __restrict__ hist, long ntiles, i64* __restrict__ totals) {
