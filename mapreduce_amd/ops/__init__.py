@@ -9,6 +9,7 @@ environments).
 from __future__ import annotations
 
 import math
+import os
 from typing import Optional
 
 import torch
@@ -807,6 +808,92 @@ def join_sorted(lkeys: torch.Tensor, rkeys: torch.Tensor,
     if max_rows is not None and total > max_rows:
         raise JoinTooLarge(total, max_rows)
     return tuple(ext().join_expand(off, lo, cnt, total))
+
+
+# ---------------------------------------------------------------------------
+# as-of join of two relations sorted on (key, time)
+# ---------------------------------------------------------------------------
+
+# caps of the windowed as-of kernel (ops/hip/asof.hip): left rows per tile,
+# right rows of a tile's window staged in LDS.  The CPU tier has no tiles; it
+# reports the same values so tests size their cases alike on both tiers.
+ASOF_TILE = 1024
+ASOF_WIN = 2048
+
+_ASOF_DIRECTIONS = {"backward": 0, "forward": 1, "nearest": 2}
+
+
+def asof_caps():
+    """-> (ASOF_TILE, ASOF_WIN): the extension's own values on a GPU
+    machine, the Python constants above on the CPU tier."""
+    if torch.cuda.is_available():
+        return tuple(int(c) for c in ext().asof_caps())
+    return ASOF_TILE, ASOF_WIN
+
+
+def _asof_tolerance(tolerance):
+    if tolerance is None:
+        return None
+    if isinstance(tolerance, bool) or not isinstance(tolerance, int):
+        raise TypeError(f"tolerance must be an int or None, got {tolerance!r}")
+    if not 0 <= tolerance < 2 ** 63:
+        raise ValueError(f"tolerance must be in [0, 2^63), got {tolerance}")
+    return tolerance
+
+
+def asof_sorted(lkeys: torch.Tensor, ltimes: torch.Tensor,
+                rkeys: torch.Tensor, rtimes: torch.Tensor,
+                direction: str = "backward", tolerance: Optional[int] = None,
+                allow_exact: bool = True) -> torch.Tensor:
+    """As-of join of two relations, each sorted ascending on (key, order key
+    of the time): keys are i64 tensors holding u64 bit patterns, times are
+    i64 or f64 (one dtype on both sides) ordered by group_order_keys.
+    Sortedness is the caller's contract and is not checked; the inputs are
+    never written.  -> ri i64[nl]: for every left row the index of the right
+    row it matches, or -1.  No host sync.
+
+    With P / Q the number of right rows < / <= the left row's (key, time):
+    "backward" takes row Q - 1, the latest right row of the key at or before
+    the time (P - 1, strictly before, when allow_exact is False); "forward"
+    takes row P, the earliest at or after it (Q, strictly after);
+    "nearest" takes the closer of the two, the backward one on a tie.  A
+    candidate of another key never matches.  In a run of right rows with
+    equal (key, time), backward takes the last and forward the first.
+
+    tolerance (i64 times only, 0 <= tolerance < 2^63): a candidate further
+    than this from the left time does not match.  The distance is the u64
+    difference of the two order keys, as in session_flags, so it cannot
+    overflow whatever the span.
+
+    Device path (ops/hip/asof.hip): a block per tile of ASOF_TILE left rows
+    searches the window of right rows its tile can reach, staged in LDS when
+    it holds at most ASOF_WIN rows.  MR_ASOF_ROW=1 (read per call) runs the
+    thread-per-row kernel over the whole right side instead, for A/B."""
+    if direction not in _ASOF_DIRECTIONS:
+        raise ValueError(
+            f"direction must be one of {tuple(_ASOF_DIRECTIONS)}, "
+            f"got {direction!r}")
+    tolerance = _asof_tolerance(tolerance)
+    if lkeys.dtype != torch.int64 or rkeys.dtype != torch.int64:
+        raise TypeError("asof: key columns must be int64")
+    if ltimes.dtype != rtimes.dtype:
+        raise TypeError(
+            "asof: both sides need one time dtype, got "
+            f"{ltimes.dtype} and {rtimes.dtype}")
+    lt, f64 = _group_vals_i64(ltimes, "ltimes")
+    rt, _ = _group_vals_i64(rtimes, "rtimes")
+    if f64 and tolerance is not None:
+        raise TypeError("asof: a tolerance needs int64 times, got float64")
+    if ltimes.numel() != lkeys.numel() or rtimes.numel() != rkeys.numel():
+        raise ValueError("one time per key required on each side")
+    if not any(t.is_cuda for t in (lkeys, ltimes, rkeys, rtimes)):
+        from . import _cpu
+        return _cpu.asof_sorted(lkeys, ltimes, rkeys, rtimes, direction,
+                                tolerance, bool(allow_exact))
+    row = os.environ.get("MR_ASOF_ROW", "0") == "1"
+    return ext().asof_sorted(lkeys, lt, rkeys, rt,
+                             _ASOF_DIRECTIONS[direction], tolerance,
+                             bool(allow_exact), f64, row)
 
 
 # ---------------------------------------------------------------------------

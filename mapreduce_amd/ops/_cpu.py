@@ -459,3 +459,55 @@ def session_flags(keys: torch.Tensor, times: torch.Tensor, gap: int):
     flags = np.ones(len(ku), dtype=np.int64)
     flags[1:] = (ku[1:] != ku[:-1]) | ((ok[1:] - ok[:-1]) > np.uint64(gap))
     return torch.from_numpy(flags)
+
+
+# ---- as-of join ------------------------------------------------------------
+
+def asof_sorted(lkeys: torch.Tensor, ltimes: torch.Tensor,
+                rkeys: torch.Tensor, rtimes: torch.Tensor, direction: str,
+                tolerance: Optional[int], allow_exact: bool):
+    """NumPy form of ops.asof_sorted (same output, row for row).  The
+    (key, order key) pairs of both sides are ranked together (np.lexsort,
+    equal pairs sharing a rank), so one np.searchsorted of the left ranks in
+    the right ones, per side, gives P and Q; the candidates are then checked
+    column-wise."""
+    lk, rk = _u64(lkeys.contiguous()), _u64(rkeys.contiguous())
+    lo, ro = group_order_keys(ltimes), group_order_keys(rtimes)
+    nl, nr = len(lk), len(rk)
+    out = np.full(nl, -1, dtype=np.int64)
+    if nl == 0 or nr == 0:
+        return torch.from_numpy(out)
+    k, o = np.concatenate([lk, rk]), np.concatenate([lo, ro])
+    order = np.lexsort((o, k))
+    sk, so = k[order], o[order]
+    step = np.ones(nl + nr, dtype=np.int64)
+    step[1:] = (sk[1:] != sk[:-1]) | (so[1:] != so[:-1])
+    rank = np.empty(nl + nr, dtype=np.int64)
+    rank[order] = np.cumsum(step)
+    p = np.searchsorted(rank[nl:], rank[:nl], side="left")
+    q = np.searchsorted(rank[nl:], rank[:nl], side="right")
+
+    def check(c, back):
+        ok = (c >= 0) & (c < nr)
+        cc = np.clip(c, 0, nr - 1)
+        ok &= rk[cc] == lk
+        dist = lo - ro[cc] if back else ro[cc] - lo  # u64; read where ok
+        if tolerance is not None:
+            ok &= dist <= np.uint64(tolerance)
+        return ok, dist
+
+    cb = (q if allow_exact else p) - 1
+    cf = p if allow_exact else q
+    if direction == "backward":
+        ok, _ = check(cb, True)
+        out[ok] = cb[ok]
+    elif direction == "forward":
+        ok, _ = check(cf, False)
+        out[ok] = cf[ok]
+    else:
+        vb, db = check(cb, True)
+        vf, df = check(cf, False)
+        out[vf] = cf[vf]
+        back = vb & (~vf | (db <= df))
+        out[back] = cb[back]
+    return torch.from_numpy(out)

@@ -12,8 +12,10 @@
 #include <limits>
 #include <map>
 #include <mutex>
+#include <optional>
 #include <utility>
 
+#include "asof.hip"
 #include "extract_sorted.hip"
 #include "gradsum.hip"
 #include "group.hip"
@@ -1476,6 +1478,60 @@ std::vector<torch::Tensor> join_expand(torch::Tensor off, torch::Tensor lo,
   return {li, ri};
 }
 
+// ----------------------------------------------------------- sorted as-of join
+// caps of the windowed as-of kernel: (left rows per tile, right rows of a
+// window staged in LDS)
+std::vector<long> asof_caps() { return {ASOF_TILE, ASOF_WIN}; }
+
+// Both sides sorted ascending on (key, order key of the time); times are
+// int64 views, f64 says they hold doubles.  -> ri i64[nl]: the matched right
+// row of every left row, or -1.  direction 0 backward, 1 forward, 2 nearest;
+// row picks the thread-per-row kernel over the block-window one (same
+// output).  No host sync.
+torch::Tensor asof_sorted(torch::Tensor lkeys, torch::Tensor ltimes,
+                          torch::Tensor rkeys, torch::Tensor rtimes,
+                          long direction, std::optional<int64_t> tolerance,
+                          bool allow_exact, bool f64, bool row) {
+  check_dev_i64(lkeys, "lkeys");
+  check_dev_i64(ltimes, "ltimes");
+  check_dev_i64(rkeys, "rkeys");
+  check_dev_i64(rtimes, "rtimes");
+  TORCH_CHECK(lkeys.device() == ltimes.device() &&
+                  lkeys.device() == rkeys.device() &&
+                  lkeys.device() == rtimes.device(),
+              "lkeys, ltimes, rkeys and rtimes must be on the same device");
+  long nl = lkeys.numel();
+  long nr = rkeys.numel();
+  TORCH_CHECK(ltimes.numel() == nl, "ltimes must hold one time per left key");
+  TORCH_CHECK(rtimes.numel() == nr, "rtimes must hold one time per right key");
+  TORCH_CHECK(direction >= ASOF_BACKWARD && direction <= ASOF_NEAREST,
+              "direction must be 0 (backward), 1 (forward) or 2 (nearest), "
+              "got ", direction);
+  TORCH_CHECK(!tolerance || *tolerance >= 0,
+              "tolerance must be in [0, 2^63), got ", tolerance.value_or(0));
+  TORCH_CHECK(!tolerance || !f64, "a tolerance needs int64 times");
+  auto ri = torch::empty({nl}, lkeys.options());
+  if (!nl) return ri;
+  const u64* rkp = nr ? u64cp(rkeys) : nullptr;
+  const u64* rtp = nr ? u64cp(rtimes) : nullptr;
+  const int has_tol = tolerance ? 1 : 0;
+  const u64 tol = (u64)tolerance.value_or(0);
+  if (row) {
+    hipLaunchKernelGGL(asof_row_kernel, dim3(grid_for(nl)), dim3(ASOF_BLOCK),
+                       0, cur_stream(), u64cp(lkeys), u64cp(ltimes), nl, rkp,
+                       rtp, nr, (int)direction, (int)allow_exact, has_tol, tol,
+                       (int)f64, ri.data_ptr<i64>());
+  } else {
+    long ntiles = (nl + ASOF_TILE - 1) / ASOF_TILE;
+    long blocks = ntiles < kMaxBlocks ? ntiles : kMaxBlocks;
+    hipLaunchKernelGGL(asof_window_kernel, dim3(blocks), dim3(ASOF_BLOCK), 0,
+                       cur_stream(), u64cp(lkeys), u64cp(ltimes), nl, rkp, rtp,
+                       nr, ntiles, (int)direction, (int)allow_exact, has_tol,
+                       tol, (int)f64, ri.data_ptr<i64>());
+  }
+  return ri;
+}
+
 // ------------------------------------------------- per-key order statistics
 // caps of the group kernels: (rows per tile, rank specifications per pick)
 std::vector<long> group_caps() { return {GROUP_TILE, GROUP_QMAX}; }
@@ -1801,6 +1857,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("join_expand", &join_expand,
         "(li, ri) row pairs from the bounds and their exclusive cumsum");
   m.def("join_caps", &join_caps, "(TILE, LDS_ROWS) of join_expand");
+  m.def("asof_sorted", &asof_sorted, py::arg("lkeys"), py::arg("ltimes"),
+        py::arg("rkeys"), py::arg("rtimes"), py::arg("direction") = 0,
+        py::arg("tolerance") = py::none(), py::arg("allow_exact") = true,
+        py::arg("f64") = false, py::arg("row") = false,
+        "matched right row (or -1) of each left row of two sorted relations");
+  m.def("asof_caps", &asof_caps, "(TILE, WIN) of the windowed asof_sorted");
   m.def("tokenizer_occupancy", &tokenizer_occupancy,
         "blocks/CU, registers and static LDS of the default tokenizer");
   m.def("postings_search", &postings_search,

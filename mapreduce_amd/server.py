@@ -86,10 +86,11 @@ class Server:
         self.stall_timeout = params.get("stall_timeout", 600.0)
         self.verbose = params.get("verbose", True)
         self.fns = FnSet(fns, self.params["init_args"])
-        # a malformed "group" or "window" family reducer is refused here,
-        # not mid-task
+        # a malformed "group", "window" or "asof" family reducer is
+        # refused here, not mid-task
         self.parse_group_reducer(self.fns.reducefn_gpu)
         self.parse_window_reducer(self.fns.reducefn_gpu)
+        self.parse_asof_reducer(self.fns.reducefn_gpu)
         self.fs = fsmod.router(storage, self.params["path"])
         return self
 
@@ -182,10 +183,64 @@ class Server:
             raise bad
         return op, int(arg)
 
+    # as-of join of two staged, time-ordered relations
+    GPU_ASOF_REDUCER = "join_asof"
+
+    @classmethod
+    def parse_asof_reducer(cls, name):
+        """reducefn_gpu of the "asof" family -> {"direction", "allow_exact",
+        "how", "tolerance"}, or None when the name belongs to another
+        family.  "join_asof" alone is backward, exact matches allowed, every
+        left row kept, no tolerance; "join_asof:OPT[,OPT...]" takes at most
+        one of backward / forward / nearest, "strict" (no exact matches),
+        "inner" (matched rows only) and "tol=N", a decimal integer with
+        0 <= N < 2^63.  A malformed name raises ValueError naming the
+        string."""
+        if not isinstance(name, str):
+            return None
+        op, sep, arg = name.partition(":")
+        if op != cls.GPU_ASOF_REDUCER:
+            return None
+        bad = ValueError(
+            f"malformed reducefn_gpu {name!r}: expected 'join_asof' or "
+            "'join_asof:OPT[,OPT...]' with each option once: one of "
+            "'backward', 'forward', 'nearest'; 'strict'; 'inner'; 'tol=N' "
+            "with a decimal 0 <= N < 2^63")
+        opts = {"direction": None, "allow_exact": True, "how": "left",
+                "tolerance": None}
+        if not sep:
+            opts["direction"] = "backward"
+            return opts
+        seen = set()
+        for part in arg.split(","):
+            if part in ("backward", "forward", "nearest"):
+                what = "direction"
+                opts["direction"] = part
+            elif part == "strict":
+                what = "strict"
+                opts["allow_exact"] = False
+            elif part == "inner":
+                what = "inner"
+                opts["how"] = "inner"
+            elif part.startswith("tol="):
+                n = part[4:]
+                if not (n.isascii() and n.isdigit() and int(n) < 2 ** 63):
+                    raise bad
+                what = "tol"
+                opts["tolerance"] = int(n)
+            else:
+                raise bad
+            if what in seen:
+                raise bad
+            seen.add(what)
+        if opts["direction"] is None:
+            opts["direction"] = "backward"
+        return opts
+
     def _gpu_engine_kind(self) -> Optional[str]:
         """Which GPU engine family this task routes to, or None.
 
-        Eight families (one worked example each; README table):
+        Nine families (one worked example each; README table):
           "bytes"   mapfn_gpu + reducefn_gpu="sum" — fused tokenize/
                     combine wordcount engine (examples/wordcount)
           "pairs"   mapfn_gpu_pairs + sum/min/max/minmax — keyed
@@ -204,6 +259,9 @@ class Server:
           "window"  mapfn_gpu_pairs + cumsum/cummin/cummax/sessions:GAP —
                     per-key running aggregates and sessions over the
                     ordered rows (examples/sessions)
+          "asof"    mapfn_gpu_pairs + join_asof[:backward|forward|nearest,
+                    strict,inner,tol=N] — as-of join of two time-ordered
+                    relations (examples/asof_quotes)
 
         MR_GPU_TIER=off forces host tier; =force routes the GPU data
         path onto the CPU-ops engine (testing without a GPU)."""
@@ -251,6 +309,11 @@ class Server:
             # running aggregates and sessions depend on the order of a
             # key's rows: not associative either, no property flags
             kind = "window"
+        elif (callable(fns.mapfn_gpu_pairs)
+              and self.parse_asof_reducer(fns.reducefn_gpu) is not None):
+            # the as-of join walks the two relations' rows of a key in
+            # time order: exact by construction, no property flags
+            kind = "asof"
         elif (callable(fns.mapfn_gpu_pairs)
               and fns.reducefn_gpu in self.GPU_PAIR_REDUCERS
               and fns.associative and fns.commutative
@@ -1055,6 +1118,145 @@ class Server:
         })
         self.print_stats()
 
+    def _loop_gpu_asof(self) -> None:
+        """As-of join GPU engine: each map job stages rows of ONE of two
+        time-ordered relations — mapfn_gpu_pairs(key, value) -> (keys,
+        times, vals, side), side 0 = left, 1 = right — and the reduce pairs
+        every left row with one right row of its key (gpu/asof.py: both
+        sides arranged by (key, time, value) and mulhi-shuffled by
+        WindowJob, ops.asof_sorted).  reducefn_gpu is "join_asof",
+        optionally followed by ":" and options (parse_asof_reducer):
+        backward / forward / nearest, strict, inner, tol=N.
+
+        finalfn receives, per key in global u64 key order,
+        (gpu_key_decode(key), [(ltime, lval, rtime, rval), ...]), the rows
+        ascending by (ltime, lval); rtime and rval are None on unmatched
+        rows, which "inner" drops.  Rank r owns the r-th contiguous range
+        of the key space (mulhi is monotonic), so the rank-major
+        concatenation is already that order.
+
+        Contract: int64-representable keys; one time and one value column
+        per side, floats staged as f64 and ints as i64, uniformly across
+        ranks; the two sides' times share one dtype."""
+        import torch
+
+        from .gpu import dist as dx
+        from .gpu.asof import AsofJoinJob
+
+        t_start = gettime()
+        rank, world = dx.world_info()
+        device = (torch.device("cuda", torch.cuda.current_device())
+                  if torch.cuda.is_available() else torch.device("cpu"))
+        name = self.fns.reducefn_gpu
+        opts = self.parse_asof_reducer(name)
+        decode = self.fns.gpu_key_decode or (lambda k: k)
+        gtask = Task(self.coord, key="task_gpu")
+        staged = None  # (job signature, six columns) — iteration reuse
+
+        def stage(col):
+            # floats stage as f64 from the start: as_tensor's default
+            # (f32) would round them before the widening; an empty list
+            # is f32 to torch and decides nothing
+            t = torch.as_tensor(col)
+            if t.is_floating_point() and t.numel():
+                return torch.as_tensor(col, dtype=torch.float64)
+            return t.to(torch.int64)
+
+        while not self.finished:
+            if rank == 0:
+                gtask.create_collection(TASK_STATUS.WAIT, {
+                    "fns": {"engine": f"asof:{opts['direction']}"},
+                    "storage": "hbm", "result_ns": "result",
+                }, self.iteration)
+            jobs = self._collect_taskfn_jobs()
+            mine = [kv for i, kv in enumerate(jobs) if i % world == rank]
+            if rank == 0:
+                gtask.set_task_status(TASK_STATUS.MAP)
+            sig = [k for k, _ in mine]
+            if staged is None or staged[0] != sig:
+                # parts[side][column]: keys, times, vals
+                parts = ([[], [], []], [[], [], []])
+                for k, v in mine:
+                    out = self.fns.mapfn_gpu_pairs(k, v)
+                    if not (isinstance(out, (tuple, list))
+                            and len(out) == 4 and out[3] in (0, 1)):
+                        raise ValueError(
+                            "mapfn_gpu_pairs must return (keys, times, vals, "
+                            f"side) under reducefn_gpu={name!r}, side 0 for "
+                            "the left relation and 1 for the right; job "
+                            f"{k!r} returned "
+                            + (f"a {len(out)}-tuple"
+                               if isinstance(out, (tuple, list))
+                               else type(out).__name__))
+                    side = out[3]
+                    parts[side][0].append(torch.as_tensor(out[0],
+                                                          dtype=torch.int64))
+                    parts[side][1].append(stage(out[1]))
+                    parts[side][2].append(stage(out[2]))
+                # a rank may stage nothing of a side yet receive its rows
+                # in the shuffle: the ranks agree on each column's dtype
+                isf = torch.tensor(
+                    [int(any(t.is_floating_point() for t in parts[s][c]))
+                     for s in (0, 1) for c in (1, 2)], dtype=torch.int64,
+                    device=device)
+                if world > 1:
+                    import torch.distributed as td
+                    td.all_reduce(isf, op=td.ReduceOp.MAX)
+                isf = isf.cpu().tolist()
+                if isf[0] != isf[2]:
+                    # the same vector on every rank: all of them raise
+                    raise TypeError(
+                        "the two relations' times must share one dtype under "
+                        f"reducefn_gpu={name!r}: the left times are "
+                        f"{'float' if isf[0] else 'int'}, the right ones "
+                        f"{'float' if isf[2] else 'int'}")
+                cols = []
+                for s in (0, 1):
+                    for c in range(3):
+                        f = isf[2 * s + c - 1] if c else 0
+                        dt = torch.float64 if f else torch.int64
+                        cols.append(
+                            torch.cat(parts[s][c]).to(dt).to(device)
+                            if parts[s][c]
+                            else torch.empty(0, dtype=dt, device=device))
+                staged = (sig, cols)
+            cols = staged[1]
+            if rank == 0:
+                gtask.set_task_status(TASK_STATUS.REDUCE)
+            res = AsofJoinJob(device, **opts).run(*cols)
+            if rank == 0:
+                gtask.set_task_status(TASK_STATUS.FINISHED)
+            # one tolist() per column, then group the rows of each key
+            keys = res.keys.cpu().tolist()
+            rts = res.rtimes.cpu().tolist()
+            rvs = res.rvals.cpu().tolist()
+            if res.matched is not None:
+                ma = res.matched.cpu().tolist()
+                rts = [t if m else None for t, m in zip(rts, ma)]
+                rvs = [v if m else None for v, m in zip(rvs, ma)]
+            rows = zip(res.ltimes.cpu().tolist(), res.lvals.cpu().tolist(),
+                       rts, rvs)
+            pairs = []
+            last = None
+            for k, row in zip(keys, rows):
+                if not pairs or k != last:
+                    pairs.append((decode(k), []))
+                    last = k
+                pairs[-1][1].append(row)
+            # rank-major concatenation IS global key order: no re-sort
+            reply = self._gpu_finalize_round(pairs, rank, world)
+            if reply == "loop":
+                self.iteration += 1
+                self._log(f"iterative loop -> iteration {self.iteration}")
+            else:
+                self.finished = True
+        self.stats.update({
+            "tier": "gpu", "engine": "asof",
+            "map_failed": 0, "reduce_failed": 0,
+            "total_time": gettime() - t_start,
+        })
+        self.print_stats()
+
     # ------------------------------------------------------------ map phase
     def _prepare_map(self) -> None:
         """server_prepare_map (server.lua:249-276): run taskfn(emit), check
@@ -1237,6 +1439,7 @@ class Server:
                   "join": self._loop_gpu_join,
                   "group": self._loop_gpu_group,
                   "window": self._loop_gpu_window,
+                  "asof": self._loop_gpu_asof,
                   "index": self._loop_gpu_index,
                   "gradsum": self._loop_gpu_grads}[kind]
             try:
