@@ -8,6 +8,8 @@ maxima, and gap-based sessions of an event log.
     res.scan("sum")                       # running amount, by time
     res.sessions(1800)                    # Sessions(keys, start, end, ...)
     res.scan("sum", within_sessions=1800)
+    res.rolling("sum", 3600)              # amount over the trailing hour
+    res.rolling("max", 99, unit="rows")   # over the trailing 100 rows
 
 Keys are i64 (u64 bit order).  The order column and the optional value
 column are i64 or f64 and ride every sort and exchange as their int64
@@ -41,6 +43,9 @@ import torch
 
 from .. import ops
 from . import dist as dx
+
+
+ROLLING_OPS = ("sum", "min", "max", "count", "mean")
 
 
 class Sessions(NamedTuple):
@@ -106,6 +111,44 @@ class OrderedRows(NamedTuple):
         per_key = torch.bincount(srow, minlength=self.keys.numel())
         return Sessions(self.keys.index_select(0, srow), start, end, en - st,
                         per_key)
+
+    def frames(self, preceding, following=0, unit: str = "range"):
+        """-> (lo, hi): the frame [lo[i], hi[i]) of every row, of rows of
+        its own key.  unit="range": the rows whose order entry lies in
+        [order - preceding, order + following], peers included
+        (ops.frame_bounds; the order column must be i64).  unit="rows": the
+        preceding rows before and the following rows behind it
+        (ops.frame_bounds_rows), which depends on how (order, value)
+        arranged the rows."""
+        if unit == "range":
+            return ops.frame_bounds(self._row_keys(), self.order, preceding,
+                                    following)
+        if unit == "rows":
+            return ops.frame_bounds_rows(self.offsets, preceding, following,
+                                         nrows=self.order.numel())
+        raise ValueError(f"unit must be 'range' or 'rows', got {unit!r}")
+
+    def rolling(self, op: str, preceding=0, following=0, unit: str = "range",
+                frames=None) -> torch.Tensor:
+        """The sum / min / max / count / mean of the value column over every
+        row's frame (ops.frame_reduce).  frames= takes a pair from frames(),
+        so several aggregates share one bounds pass; preceding, following
+        and unit are not read then.  count is i64 and needs no value column;
+        mean is f64, sum / count with an i64 sum converted after
+        wrapping."""
+        if op not in ROLLING_OPS:
+            raise ValueError(
+                f"op must be one of {ROLLING_OPS}, got {op!r}")
+        if op != "count" and self.values is None:
+            raise ValueError("rolling needs a value column")
+        lo, hi = (frames if frames is not None
+                  else self.frames(preceding, following, unit))
+        if op == "count":
+            return hi - lo
+        if op != "mean":
+            return ops.frame_reduce(self.values, lo, hi, op)
+        total = ops.frame_reduce(self.values, lo, hi, "sum")
+        return total.to(torch.float64) / (hi - lo).to(torch.float64)
 
     def to_host(self) -> List[Tuple[int, list]]:
         """[(key as i64, [(order, value), ...])] in key order, the rows

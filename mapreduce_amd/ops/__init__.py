@@ -1283,3 +1283,171 @@ def group_sessions(keys_sorted: torch.Tensor, sorted_times: torch.Tensor,
     soffsets[s]:soffsets[s + 1].  One host sync (the session count)."""
     flags = session_flags(keys_sorted, sorted_times, gap)
     return _group_offsets(keys_sorted, flags)
+
+
+# ---------------------------------------------------------------------------
+# per-key rolling aggregates over (key, time)-sorted rows: every row gets a
+# frame of rows of its own key and an aggregate over it
+# ---------------------------------------------------------------------------
+
+# caps of the frame kernels (ops/hip/frame.hip): rows per tile of the window
+# bounds kernel, rows of a tile's window staged in LDS, rows per tile of the
+# reduce kernels.  The CPU tier has no tiles; it reports the same values so
+# tests size their cases alike on both tiers.
+FRAME_TILE = 1024
+FRAME_WIN = 2048
+FRAME_RTILE = 2048
+FRAME_MAX_ROW_EXTENT = 2 ** 31
+# which bounds kernel runs when MR_FRAME_ROW is unset: the measured winner
+# on the benchmark shapes (profiles/rolling.md)
+_FRAME_ROW_DEFAULT = "1"
+
+
+def frame_caps():
+    """-> (FRAME_TILE, FRAME_WIN, FRAME_RTILE): the extension's own values
+    on a GPU machine, the Python constants above on the CPU tier."""
+    if torch.cuda.is_available():
+        return tuple(int(c) for c in ext().frame_caps())
+    return FRAME_TILE, FRAME_WIN, FRAME_RTILE
+
+
+def frame_tree_levels(ntiles: int):
+    """The node counts of the tree frame_reduce builds over ntiles tile
+    aggregates, level 0 (the tiles) first: level l holds the ntiles >> l
+    nodes whose 2^l tiles all exist.  ext().frame_tree returns the levels
+    one behind the other."""
+    out = []
+    while ntiles >= 1:
+        out.append(ntiles)
+        ntiles >>= 1
+    return out
+
+
+def _frame_extent(x, name: str, limit: int, limit_name: str) -> int:
+    if isinstance(x, bool) or not isinstance(x, int):
+        raise TypeError(f"{name} must be an int, got {x!r}")
+    if not 0 <= x < limit:
+        raise ValueError(f"{name} must be in [0, {limit_name}), got {x}")
+    return x
+
+
+def frame_bounds(keys_sorted: torch.Tensor, sorted_times: torch.Tensor,
+                 preceding: int, following: int = 0):
+    """Range frames of a relation sorted ascending on (key, order key of the
+    time), the contract of asof_sorted: keys are i64 tensors holding u64 bit
+    patterns, times are i64 (f64 is refused with a TypeError, as for
+    session_flags).  Sortedness is the caller's contract and is not checked;
+    the inputs are never written.  -> (lo, hi), i64[n] each: the frame of
+    row i is the rows lo[i] <= j < hi[i], with lo[i] <= i < hi[i].  No host
+    sync.
+
+    preceding and following are Python ints in [0, 2^63).  With T the order
+    key of row i's time, the frame holds every row of i's key whose order
+    key lies in [sat(T - preceding), sat(T + following)], both ends
+    inclusive and computed in u64, saturating at 0 and 2^64 - 1, so no span
+    can overflow.  This is SQL's RANGE BETWEEN preceding PRECEDING AND
+    following FOLLOWING: rows with the time of row i (its peers) are always
+    in its frame, those behind it too, so an aggregate over a range frame
+    depends on the multiset of (time, value) alone.  lo and hi are
+    non-decreasing along the rows and a frame never crosses a key.
+
+    Device path (ops/hip/frame.hip): a thread per row brackets each end by
+    an exponential search outward from the row itself, then bisects the
+    bracket.  MR_FRAME_ROW=0 (read per call) runs the block-window kernel
+    in the shape of asof_sorted's instead (tiles of FRAME_TILE rows, a
+    window of at most FRAME_WIN rows staged in LDS), for A/B; the two give
+    the same output."""
+    preceding = _frame_extent(preceding, "preceding", 2 ** 63, "2^63")
+    following = _frame_extent(following, "following", 2 ** 63, "2^63")
+    if sorted_times.dtype != torch.int64:
+        raise TypeError(
+            f"range frames need int64 times, got {sorted_times.dtype}")
+    if keys_sorted.dtype != torch.int64:
+        raise TypeError("keys must be int64")
+    if sorted_times.numel() != keys_sorted.numel():
+        raise ValueError("one time per key required")
+    _group_check_rows(keys_sorted.numel())
+    if not keys_sorted.is_cuda and not sorted_times.is_cuda:
+        from . import _cpu
+        return _cpu.frame_bounds(keys_sorted, sorted_times, preceding,
+                                 following)
+    row = os.environ.get("MR_FRAME_ROW", _FRAME_ROW_DEFAULT) == "1"
+    lo, hi = ext().frame_bounds(keys_sorted, sorted_times, preceding,
+                                following, row)
+    return lo, hi
+
+
+def frame_bounds_rows(offsets: torch.Tensor, preceding: int,
+                      following: int = 0, nrows: Optional[int] = None):
+    """Row frames (SQL's ROWS BETWEEN preceding PRECEDING AND following
+    FOLLOWING) from the offsets of group_by_key_sorted: for row i of the key
+    that owns rows [s, e), lo = max(s, i - preceding) and
+    hi = min(e, i + following + 1).  preceding and following are Python
+    ints in [0, 2^31).  -> (lo, hi), i64[n] each, on the device of offsets.
+
+    Plain torch on the offsets (a repeat_interleave, an arange and two
+    clamps): every row's answer is arithmetic on its own index and its
+    key's two offsets, with nothing to search, so it is not worth a kernel.
+    nrows = the row count offsets[-1] when the caller knows it; without it
+    the count is read back (one host sync)."""
+    preceding = _frame_extent(preceding, "preceding", FRAME_MAX_ROW_EXTENT,
+                              "2^31")
+    following = _frame_extent(following, "following", FRAME_MAX_ROW_EXTENT,
+                              "2^31")
+    if offsets.dtype != torch.int64:
+        raise TypeError("offsets must be int64")
+    _group_check_offsets(offsets)
+    if nrows is None:
+        nrows = int(offsets[-1])
+    _group_check_rows(nrows)
+    seg = torch.repeat_interleave(
+        torch.arange(offsets.numel() - 1, device=offsets.device),
+        offsets[1:] - offsets[:-1], output_size=nrows)
+    i = torch.arange(nrows, device=offsets.device)
+    lo = torch.maximum(i - preceding, offsets[:-1].index_select(0, seg))
+    hi = torch.minimum(i + (following + 1), offsets[1:].index_select(0, seg))
+    return lo, hi
+
+
+def frame_reduce(vals: torch.Tensor, lo: torch.Tensor, hi: torch.Tensor,
+                 op: str = "sum") -> torch.Tensor:
+    """out[i] = the sum, minimum or maximum of vals over the rows
+    lo[i] <= j < hi[i], for frames with lo[i] <= i < hi[i] as frame_bounds
+    and frame_bounds_rows make them.  vals is i64 or f64, lo and hi i64, one
+    per value; the result has the dtype and length of vals and the inputs
+    are never written.  It needs no keys: a frame never crosses one.  No
+    host sync.
+
+    i64 sums wrap modulo 2^64.  f64 sums are IEEE over the rows of the frame
+    only, in the kernel's own association: the pieces combined for a frame
+    are disjoint and lie inside it (never a difference of running sums), so
+    the error is bounded by the frame's own sum |v| and a NaN or an inf
+    affects exactly the frames that contain it.  min / max compare by
+    group_order_keys (-0.0 equals +0.0, NaN is the largest value) and return
+    the stored bits of the earliest row of the frame among those with the
+    winning order key.
+
+    A frame that breaks the contract is clamped, lo to [0, i] and hi to
+    [i + 1, n], on both tiers: it gives a defined answer and never
+    addresses outside the column.
+
+    Device path (ops/hip/frame.hip): prefix and suffix aggregates inside
+    tiles of FRAME_RTILE rows and an aligned binary tree over the tile
+    aggregates; a frame inside one tile is a query of a tree built over the
+    tile in LDS, a longer one is suffix + whole tiles from the tile tree +
+    prefix.  Three launches ordered by their boundaries alone, fewer than
+    2^31 rows.  The CPU tier aggregates every frame directly (f64 sums by
+    math.fsum), so f64 sums may differ from the device in the last bits."""
+    if op not in _SEG_SCAN_OPS:
+        raise ValueError(f"op must be 'sum', 'min' or 'max', got {op!r}")
+    v, f64 = _group_vals_i64(vals)
+    if lo.dtype != torch.int64 or hi.dtype != torch.int64:
+        raise TypeError("lo and hi must be int64")
+    if lo.numel() != vals.numel() or hi.numel() != vals.numel():
+        raise ValueError("one lo and one hi per value required")
+    _group_check_rows(vals.numel())
+    if not vals.is_cuda and not lo.is_cuda and not hi.is_cuda:
+        from . import _cpu
+        return _cpu.frame_reduce(vals, lo, hi, op)
+    return ext().frame_reduce(v, lo, hi, _SEG_SCAN_OPS[op],
+                              f64).view(vals.dtype)

@@ -511,3 +511,66 @@ def asof_sorted(lkeys: torch.Tensor, ltimes: torch.Tensor,
         back = vb & (~vf | (db <= df))
         out[back] = cb[back]
     return torch.from_numpy(out)
+
+
+# ---- per-key rolling aggregates --------------------------------------------
+
+def frame_bounds(keys: torch.Tensor, times: torch.Tensor, preceding: int,
+                 following: int):
+    """Range frames from the definition: within each run of equal keys the
+    order keys ascend, so np.searchsorted of the two saturated ends, left
+    for lo and right for hi, gives the frame."""
+    ku = _u64(keys.contiguous())
+    ok = group_order_keys(times)
+    n = len(ku)
+    lo = np.empty(n, dtype=np.int64)
+    hi = np.empty(n, dtype=np.int64)
+    if n:
+        pre, fol = np.uint64(preceding), np.uint64(following)
+        tlo = np.where(ok >= pre, ok - pre, np.uint64(0))
+        thi = ok + fol
+        thi[thi < ok] = _ONES
+        heads = np.flatnonzero(np.concatenate([[True], ku[1:] != ku[:-1]]))
+        ends = np.concatenate([heads[1:], [n]])
+        for a, b in zip(heads.tolist(), ends.tolist()):
+            lo[a:b] = a + np.searchsorted(ok[a:b], tlo[a:b], side="left")
+            hi[a:b] = a + np.searchsorted(ok[a:b], thi[a:b], side="right")
+    return torch.from_numpy(lo), torch.from_numpy(hi)
+
+
+def frame_reduce(vals: torch.Tensor, lo: torch.Tensor, hi: torch.Tensor,
+                 op: str):
+    """Every frame aggregated on its own, lo clamped to [0, i] and hi to
+    [i + 1, n] first: i64 sums wrap, f64 sums are math.fsum (non-finite
+    frames by np.sum, which gives the IEEE inf / NaN), min / max take the
+    first row of the frame with the winning order key."""
+    import math
+    v = vals.contiguous()
+    n = v.numel()
+    out = torch.empty_like(v)
+    if n == 0:
+        return out
+    i = np.arange(n, dtype=np.int64)
+    l = np.clip(lo.numpy(), 0, i).tolist()
+    h = np.clip(hi.numpy(), i + 1, n).tolist()
+    if op == "sum" and v.dtype == torch.float64:
+        src, dst = v.numpy(), out.numpy()
+        finite = np.isfinite(src)
+        with np.errstate(all="ignore"):
+            for r in range(n):
+                w = src[l[r]:h[r]]
+                dst[r] = (math.fsum(w) if finite[l[r]:h[r]].all()
+                          else np.sum(w))
+        return out
+    if op == "sum":
+        src, dst = _u64(v), _u64(out)
+        run = np.concatenate([[np.uint64(0)], np.cumsum(src)])  # mod 2^64
+        dst[:] = run[h] - run[l]
+        return out
+    ok = group_order_keys(v)
+    bits = _u64(v.view(torch.int64))
+    dst = _u64(out.view(torch.int64))
+    pick = np.argmin if op == "min" else np.argmax  # first occurrence
+    for r in range(n):
+        dst[r] = bits[l[r] + int(pick(ok[l[r]:h[r]]))]
+    return out

@@ -17,6 +17,7 @@
 
 #include "asof.hip"
 #include "extract_sorted.hip"
+#include "frame.hip"
 #include "gradsum.hip"
 #include "group.hip"
 #include "join.hip"
@@ -1807,6 +1808,135 @@ torch::Tensor session_flags(torch::Tensor keys, torch::Tensor times,
   return flags;
 }
 
+// ------------------------------------------------- per-key rolling aggregates
+// caps of the frame kernels: (rows per tile of the window bounds kernel, rows
+// of a window staged in LDS, rows per tile of the reduce kernels)
+std::vector<long> frame_caps() { return {FRAME_TILE, FRAME_WIN, FRAME_RTILE}; }
+
+namespace {
+static_assert(FRAME_BLOCK == SEG_SCAN_BLOCK,
+              "the frame kernels are launched by SEG_SCAN_LAUNCH");
+
+long check_frame_op(const torch::Tensor& vals, long op) {
+  check_dev_i64(vals, "vals");
+  long n = vals.numel();
+  TORCH_CHECK(n < (1L << 31), "frame ops take fewer than 2^31 rows, got ", n);
+  TORCH_CHECK(op >= SEG_SUM && op <= SEG_MAX,
+              "op must be 0 (sum), 1 (min) or 2 (max), got ", op);
+  return n;
+}
+
+void check_frame_col(const torch::Tensor& t, const torch::Tensor& like,
+                     long n, const char* name) {
+  check_dev_i64(t, name);
+  TORCH_CHECK(t.device() == like.device(), name,
+              " must be on the device of the rows");
+  TORCH_CHECK(t.numel() == n, name, " must hold ", n, " entries, got ",
+              t.numel());
+}
+}  // namespace
+
+// Rows sorted ascending on (key, order key of the i64 time).  -> (lo, hi)
+// i64[n]: row i's frame is the rows [lo[i], hi[i]) of its key whose time lies
+// in [t_i - preceding, t_i + following], both ends saturating.  row picks
+// the thread-per-row kernel over the block-window one (same output).  No
+// host sync.
+std::vector<torch::Tensor> frame_bounds(torch::Tensor keys,
+                                        torch::Tensor times, long preceding,
+                                        long following, bool row) {
+  check_dev_i64(keys, "keys");
+  check_dev_i64(times, "times");
+  TORCH_CHECK(keys.device() == times.device(),
+              "keys and times must be on the same device");
+  long n = keys.numel();
+  TORCH_CHECK(times.numel() == n, "times must hold one time per key");
+  TORCH_CHECK(n < (1L << 31), "frame ops take fewer than 2^31 rows, got ", n);
+  TORCH_CHECK(preceding >= 0, "preceding must be in [0, 2^63), got ",
+              preceding);
+  TORCH_CHECK(following >= 0, "following must be in [0, 2^63), got ",
+              following);
+  auto lo = torch::empty({n}, keys.options());
+  auto hi = torch::empty({n}, keys.options());
+  if (!n) return {lo, hi};
+  if (row) {
+    hipLaunchKernelGGL(frame_bounds_row_kernel, dim3(grid_for(n)),
+                       dim3(FRAME_BLOCK), 0, cur_stream(), u64cp(keys),
+                       u64cp(times), n, (u64)preceding, (u64)following,
+                       lo.data_ptr<i64>(), hi.data_ptr<i64>());
+  } else {
+    long ntiles = (n + FRAME_TILE - 1) / FRAME_TILE;
+    long blocks = ntiles < kMaxBlocks ? ntiles : kMaxBlocks;
+    hipLaunchKernelGGL(frame_bounds_window_kernel, dim3(blocks),
+                       dim3(FRAME_BLOCK), 0, cur_stream(), u64cp(keys),
+                       u64cp(times), n, ntiles, (u64)preceding,
+                       (u64)following, lo.data_ptr<i64>(),
+                       hi.data_ptr<i64>());
+  }
+  return {lo, hi};
+}
+
+// Pass 1 of frame_reduce: (pre, suf) i64[n], the aggregate from the first
+// row of a row's tile of FRAME_RTILE rows up to the row and from the row to
+// the tile's last row, and tiles i64[ntiles], the tiles' own aggregates.
+// vals is the int64 view of an i64 or f64 column.
+std::vector<torch::Tensor> frame_tile(torch::Tensor vals, long op, bool f64) {
+  long n = check_frame_op(vals, op);
+  long ntiles = (n + FRAME_RTILE - 1) / FRAME_RTILE;
+  auto pre = torch::empty({n}, vals.options());
+  auto suf = torch::empty({n}, vals.options());
+  auto tiles = torch::empty({ntiles}, vals.options());
+  if (ntiles)
+    SEG_SCAN_LAUNCH(frame_tile_kernel, ntiles, u64cp(vals), n, u64p(pre),
+                    u64p(suf), u64p(tiles));
+  return {pre, suf, tiles};
+}
+
+// Pass 2: the aligned binary tree over the tile aggregates, by one block:
+// level l holds the ntiles >> l nodes whose 2^l tiles all exist, the levels
+// one behind the other from level 0 (the tiles themselves) up.
+torch::Tensor frame_tree(torch::Tensor tiles, long op, bool f64) {
+  long ntiles = check_frame_op(tiles, op);
+  auto tree = torch::empty({frame_tree_size(ntiles)}, tiles.options());
+  if (ntiles)
+    SEG_SCAN_LAUNCH(frame_tree_kernel, 1, u64cp(tiles), ntiles, u64p(tree));
+  return tree;
+}
+
+// Pass 3: out[i] = op over vals[lo[i]:hi[i]], lo clamped to [0, i] and hi to
+// [i + 1, n].
+torch::Tensor frame_apply(torch::Tensor vals, torch::Tensor lo,
+                          torch::Tensor hi, torch::Tensor pre,
+                          torch::Tensor suf, torch::Tensor tree, long op,
+                          bool f64) {
+  long n = check_frame_op(vals, op);
+  check_frame_col(lo, vals, n, "lo");
+  check_frame_col(hi, vals, n, "hi");
+  check_frame_col(pre, vals, n, "pre");
+  check_frame_col(suf, vals, n, "suf");
+  long ntiles = (n + FRAME_RTILE - 1) / FRAME_RTILE;
+  check_frame_col(tree, vals, frame_tree_size(ntiles), "tree");
+  auto out = torch::empty({n}, vals.options());
+  if (ntiles)
+    SEG_SCAN_LAUNCH(frame_apply_kernel, ntiles, u64cp(vals),
+                    lo.data_ptr<i64>(), hi.data_ptr<i64>(), n, u64cp(pre),
+                    u64cp(suf), u64cp(tree), ntiles, u64p(out));
+  return out;
+}
+
+// out[i] = op over the rows lo[i] <= j < hi[i] of vals, the earlier row
+// first; every frame holds its own row.  Three launches, no host sync; the
+// inputs are never written.
+torch::Tensor frame_reduce(torch::Tensor vals, torch::Tensor lo,
+                           torch::Tensor hi, long op, bool f64) {
+  long n = check_frame_op(vals, op);
+  check_frame_col(lo, vals, n, "lo");
+  check_frame_col(hi, vals, n, "hi");
+  if (!n) return torch::empty({0}, vals.options());
+  auto t = frame_tile(vals, op, f64);
+  auto tree = frame_tree(t[2], op, f64);
+  return frame_apply(vals, lo, hi, t[0], t[1], tree, op, f64);
+}
+
 // Occupancy of the default word-count tokenizer instantiation on the
 // current device, as the runtime sees it (blocks/CU clips the grid; the
 // register count and static LDS are what decide it).
@@ -1845,6 +1975,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "pass 3 of scan_by_key_sorted: the running column");
   m.def("session_flags", &session_flags,
         "1 where a row starts a key or follows a gap in time");
+  m.def("frame_caps", &frame_caps,
+        "(TILE, WIN, RTILE) of the frame kernels");
+  m.def("frame_bounds", &frame_bounds, py::arg("keys"), py::arg("times"),
+        py::arg("preceding"), py::arg("following"), py::arg("row") = false,
+        "range frames of (key, time)-sorted rows -> (lo, hi)");
+  m.def("frame_reduce", &frame_reduce,
+        "sum / min / max of a value column over per-row frames");
+  m.def("frame_tile", &frame_tile,
+        "frame_reduce pass 1: (pre, suf, tile aggregates)");
+  m.def("frame_tree", &frame_tree,
+        "frame_reduce pass 2: the tree over the tile aggregates");
+  m.def("frame_apply", &frame_apply,
+        "frame_reduce pass 3: one range query per row");
   m.def("group_pick", &group_pick,
         "values at exact rank fractions of each ordered segment");
   m.def("group_distinct_flags", &group_distinct_flags,

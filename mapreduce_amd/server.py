@@ -165,11 +165,14 @@ class Server:
         """reducefn_gpu of the "window" family -> (op, parameter), or None
         when the name belongs to another family.  "cumsum", "cummin" and
         "cummax" take no parameter; "sessions:GAP" gives GAP, a decimal
-        integer with 0 <= GAP < 2^63.  A malformed name raises ValueError
-        naming the string."""
+        integer with 0 <= GAP < 2^63; "rolling:OP:PRE[,fol=N][,rows]" gives
+        {"op", "preceding", "following", "unit"} (_parse_rolling).  A
+        malformed name raises ValueError naming the string."""
         if not isinstance(name, str):
             return None
         op, sep, arg = name.partition(":")
+        if op == "rolling":
+            return op, cls._parse_rolling(name, arg)
         if op not in cls.GPU_WINDOW_REDUCERS:
             return None
         bad = ValueError(
@@ -182,6 +185,46 @@ class Server:
         if not (arg.isascii() and arg.isdigit() and int(arg) < 2 ** 63):
             raise bad
         return op, int(arg)
+
+    GPU_ROLLING_OPS = ("sum", "min", "max", "count", "mean")
+
+    @classmethod
+    def _parse_rolling(cls, name, arg):
+        """The part of "rolling:OP:PRE[,fol=N][,rows]" behind "rolling:" ->
+        {"op", "preceding", "following", "unit"}.  OP is one of
+        GPU_ROLLING_OPS; PRE and N are decimal integers, below 2^63 for a
+        range frame and below 2^31 with "rows"; each option appears at most
+        once."""
+        bad = ValueError(
+            f"malformed reducefn_gpu {name!r}: expected "
+            "'rolling:OP:PRE[,fol=N][,rows]' with OP one of "
+            f"{'/'.join(cls.GPU_ROLLING_OPS)} and decimal PRE and N, below "
+            "2^63 (2^31 with 'rows')")
+
+        def num(txt):
+            if not (txt.isascii() and txt.isdigit()):
+                raise bad
+            return int(txt)
+
+        agg, sep, rest = arg.partition(":")
+        if agg not in cls.GPU_ROLLING_OPS or not sep:
+            raise bad
+        pre, *opts = rest.split(",")
+        out = {"op": agg, "preceding": num(pre), "following": None,
+               "unit": None}
+        for o in opts:
+            if o == "rows" and out["unit"] is None:
+                out["unit"] = "rows"
+            elif o.startswith("fol=") and out["following"] is None:
+                out["following"] = num(o[4:])
+            else:
+                raise bad
+        out["following"] = out["following"] or 0
+        out["unit"] = out["unit"] or "range"
+        limit = 2 ** 31 if out["unit"] == "rows" else 2 ** 63
+        if out["preceding"] >= limit or out["following"] >= limit:
+            raise bad
+        return out
 
     # as-of join of two staged, time-ordered relations
     GPU_ASOF_REDUCER = "join_asof"
@@ -256,9 +299,10 @@ class Server:
           "group"   mapfn_gpu_pairs + group/median/quantile:N/D,.../
                     topk:K/bottomk:K/distinct — per-key order statistics
                     over the whole value list (examples/percentiles)
-          "window"  mapfn_gpu_pairs + cumsum/cummin/cummax/sessions:GAP —
-                    per-key running aggregates and sessions over the
-                    ordered rows (examples/sessions)
+          "window"  mapfn_gpu_pairs + cumsum/cummin/cummax/sessions:GAP/
+                    rolling:OP:PRE[,fol=N][,rows] — per-key running and
+                    rolling aggregates and sessions over the ordered rows
+                    (examples/sessions, examples/rolling_spend)
           "asof"    mapfn_gpu_pairs + join_asof[:backward|forward|nearest,
                     strict,inner,tol=N] — as-of join of two time-ordered
                     relations (examples/asof_quotes)
@@ -1013,6 +1057,15 @@ class Server:
               (key, [(start, end, count), ...]), one triple per session: a
               row opens a session when it starts its key or its time
               exceeds the previous one by more than GAP
+          "rolling:OP:PRE[,fol=N][,rows]"
+              OP = sum / min / max / mean: mapfn_gpu_pairs returns (keys,
+              order, vals); OP = count: (keys, times).  finalfn receives
+              (key, [(order, rolling), ...]), the rows ascending by
+              (order, value) and rolling = OP over the row's frame
+              (OrderedRows.rolling): the rows of the key whose order entry
+              lies in [order - PRE, order + N], or with "rows" the PRE rows
+              before it and the N rows behind it.  A range frame over a
+              float order column raises the TypeError of ops.frame_bounds.
 
         finalfn receives the pairs in global u64 key order: rank r owns the
         r-th contiguous range of the key space.
@@ -1030,9 +1083,9 @@ class Server:
                   if torch.cuda.is_available() else torch.device("cpu"))
         name = self.fns.reducefn_gpu
         op, arg = self.parse_window_reducer(name)
-        ncols = 2 if op == "sessions" else 3
-        what = ("(keys, times)" if op == "sessions"
-                else "(keys, order, vals)")
+        two = op == "sessions" or (op == "rolling" and arg["op"] == "count")
+        ncols = 2 if two else 3
+        what = "(keys, times)" if two else "(keys, order, vals)"
         decode = self.fns.gpu_key_decode or (lambda k: k)
         gtask = Task(self.coord, key="task_gpu")
         staged = None  # (job signature, columns) — iteration reuse
@@ -1096,7 +1149,12 @@ class Server:
             if op == "sessions":
                 host = res.sessions(arg).to_host()
             else:
-                run = res.scan(self.GPU_WINDOW_REDUCERS[op]).cpu().tolist()
+                if op == "rolling":
+                    run = res.rolling(arg["op"], arg["preceding"],
+                                      arg["following"], arg["unit"])
+                else:
+                    run = res.scan(self.GPU_WINDOW_REDUCERS[op])
+                run = run.cpu().tolist()
                 off = res.offsets.cpu().tolist()
                 rows = list(zip(res.order.cpu().tolist(), run))
                 host = [(k, rows[off[s]:off[s + 1]])
