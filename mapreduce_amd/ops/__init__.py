@@ -1451,3 +1451,129 @@ def frame_reduce(vals: torch.Tensor, lo: torch.Tensor, hi: torch.Tensor,
         return _cpu.frame_reduce(vals, lo, hi, op)
     return ext().frame_reduce(v, lo, hi, _SEG_SCAN_OPS[op],
                               f64).view(vals.dtype)
+
+
+# ---------------------------------------------------------------------------
+# resident-graph propagation (K4/K5 for iterative reducers over keyed data:
+# every key reduces a value gathered from other keys over its edge list)
+# ---------------------------------------------------------------------------
+
+# caps of the graph kernels (ops/hip/graph.hip): edges per tile, most blocks
+# (and rows of partials) of the PageRank update pass.  The CPU tier has no
+# tiles; it reports the same values so tests size their cases alike.
+GRAPH_TILE = 2048
+GRAPH_PR_BLOCKS = 1024
+
+_GRAPH_IDENTITY = {"sum": 0, "min": 2 ** 63 - 1, "max": -2 ** 63}
+
+
+def graph_caps():
+    """-> (GRAPH_TILE, GRAPH_PR_BLOCKS): the extension's own values on a GPU
+    machine, the Python constants above on the CPU tier."""
+    if torch.cuda.is_available():
+        return tuple(int(c) for c in ext().graph_caps())
+    return GRAPH_TILE, GRAPH_PR_BLOCKS
+
+
+def _graph_propagate_composed(offsets, src, x, op, dst=None):
+    """The contract of graph_propagate composed from the project's other
+    ops: materialise the gathered column, reduce it by the destination of
+    every edge, scatter the rows that have edges.  src must be in range.
+    dst = the sorted destination column when the caller keeps it (the
+    benchmark does); it is rebuilt from offsets otherwise."""
+    n, m = x.numel(), src.numel()
+    out = torch.full((n,), 0.0 if x.dtype == torch.float64
+                     else _GRAPH_IDENTITY[op], dtype=x.dtype, device=x.device)
+    if n == 0 or m == 0:
+        return out
+    if dst is None:
+        dst = torch.repeat_interleave(
+            torch.arange(n, device=x.device), offsets[1:] - offsets[:-1],
+            output_size=m)
+    vals = x.index_select(0, src)
+    uk, uv, _, _ = reduce_by_key_sorted(dst, vals, op=op)
+    out[uk] = uv
+    return out
+
+
+def graph_propagate(offsets: torch.Tensor, src: torch.Tensor,
+                    x: torch.Tensor, op: str = "sum") -> torch.Tensor:
+    """out[v] = the sum, minimum or maximum of x[src[e]] over the in-edges
+    offsets[v] <= e < offsets[v + 1] of row v.  offsets is i64[n + 1], the
+    CSR row starts by destination (non-decreasing, offsets[0] = 0,
+    offsets[n] = m; the caller's contract, not checked); src is int32[m],
+    dense source ids in [0, n); x is i64 or f64 [n].  The result has the
+    dtype and length of x and the inputs are never written.  No host sync;
+    fewer than 2^31 edges and rows.
+
+    "sum": i64 wraps modulo 2^64, f64 is IEEE.  "min" / "max": i64 only
+    (signed); f64 raises TypeError.  An empty row gives the identity: 0,
+    INT64_MAX or INT64_MIN.  A src entry outside [0, n) contributes the
+    identity and is never dereferenced; offsets that break the contract give
+    an unspecified but defined answer and never address outside src, x or
+    out.
+
+    Device path (ops/hip/graph.hip): tiles of GRAPH_TILE edges whatever the
+    rows look like, so a hub is spread over many blocks and empty rows cost
+    nothing; rows inside a tile are finished there, rows across tiles by a
+    one-block scan of the tile aggregates.  No atomics: the association of
+    a row's f64 sum depends on (offsets, m) alone, so two calls return the
+    same bits.  The CPU tier sums f64 rows by math.fsum, so it may differ
+    from the device in the last bits.
+
+    MR_GRAPH_COMPOSED=1 (read per call) runs the same contract composed
+    from index_select, reduce_by_key_sorted and a scatter instead, for A/B
+    and as an oracle on the device; its f64 sums go through atomics and are
+    not reproducible, and it needs every src in range."""
+    if op not in _SEG_SCAN_OPS:
+        raise ValueError(f"op must be 'sum', 'min' or 'max', got {op!r}")
+    v, f64 = _group_vals_i64(x, "x")
+    if f64 and op != "sum":
+        raise TypeError(f"graph {op} needs int64 values, got {x.dtype}")
+    if offsets.dtype != torch.int64:
+        raise TypeError("offsets must be int64")
+    if src.dtype != torch.int32:
+        raise TypeError(f"src must be int32, got {src.dtype}")
+    if offsets.numel() != x.numel() + 1:
+        raise ValueError(
+            f"offsets must hold {x.numel() + 1} entries for {x.numel()} "
+            f"rows, got {offsets.numel()}")
+    _group_check_rows(x.numel())
+    _group_check_rows(src.numel())
+    if not offsets.is_cuda and not src.is_cuda and not x.is_cuda:
+        from . import _cpu
+        return _cpu.graph_propagate(offsets, src, x, op)
+    if os.environ.get("MR_GRAPH_COMPOSED", "0") == "1":
+        return _graph_propagate_composed(offsets, src, x, op)
+    return ext().graph_propagate(offsets.contiguous(), src.contiguous(),
+                                 v.contiguous(), _SEG_SCAN_OPS[op],
+                                 f64).view(x.dtype)
+
+
+def pagerank_update(sums: torch.Tensor, old: torch.Tensor,
+                    inv_out: torch.Tensor, damping: float,
+                    dangling: torch.Tensor):
+    """One PageRank update over the n nodes, all f64:
+    new = (1 - d) / n + d * (sums + dangling / n), contrib = new * inv_out
+    (inv_out is 1 / outdeg, 0 for a node without out-edges).  -> (new,
+    contrib, partials): partials is f64[blocks, 2] whose column 0 sums to
+    |new - old|_1 and column 1 to the rank held by the nodes with inv_out
+    == 0 (the next iteration's dangling mass); torch.sum over the block axis
+    finishes them in a fixed order.  dangling is a 0-dim tensor on the
+    device of sums, so iterations chain with no host sync."""
+    for name, t in (("sums", sums), ("old", old), ("inv_out", inv_out),
+                    ("dangling", dangling)):
+        if t.dtype != torch.float64:
+            raise TypeError(f"{name} must be float64, got {t.dtype}")
+    if old.numel() != sums.numel() or inv_out.numel() != sums.numel():
+        raise ValueError("one old rank and one inv_out per sum required")
+    if dangling.numel() != 1:
+        raise ValueError("dangling must hold one value")
+    if not sums.is_cuda and not old.is_cuda and not inv_out.is_cuda:
+        from . import _cpu
+        return _cpu.pagerank_update(sums, old, inv_out, float(damping),
+                                    dangling)
+    new, contrib, partials = ext().pagerank_update(
+        sums.contiguous(), old.contiguous(), inv_out.contiguous(),
+        float(damping), dangling.reshape(1))
+    return new, contrib, partials

@@ -574,3 +574,61 @@ def frame_reduce(vals: torch.Tensor, lo: torch.Tensor, hi: torch.Tensor,
     for r in range(n):
         dst[r] = bits[l[r] + int(pick(ok[l[r]:h[r]]))]
     return out
+
+
+_GRAPH_IDENTITY = {"sum": 0, "min": np.iinfo(np.int64).max,
+                   "max": np.iinfo(np.int64).min}
+
+
+def graph_propagate(offsets: torch.Tensor, src: torch.Tensor,
+                    x: torch.Tensor, op: str):
+    """Every row aggregated on its own over its in-edges: i64 sums wrap,
+    f64 sums are math.fsum (rows holding a non-finite value by np.sum, which
+    gives the IEEE inf / NaN), min / max are the signed i64 ones.  A src
+    outside [0, n) contributes the identity; offsets are clamped to [0, m]
+    and a row's end to its start, so every answer is defined."""
+    import math
+    xv = x.contiguous()
+    n, m = xv.numel(), src.numel()
+    f64 = xv.dtype == torch.float64
+    ident = 0.0 if f64 else _GRAPH_IDENTITY[op]
+    out = torch.full((n,), ident, dtype=xv.dtype)
+    if n == 0 or m == 0:
+        return out
+    off = np.clip(offsets.numpy(), 0, m)
+    lo, hi = off[:-1], np.maximum(off[1:], off[:-1])
+    s = src.numpy().astype(np.int64)
+    ok = (s >= 0) & (s < n)
+    g = np.where(ok, xv.numpy()[np.where(ok, s, 0)],
+                 np.asarray(ident, dtype=xv.numpy().dtype))
+    rows = np.nonzero(hi > lo)[0]
+    dst = out.numpy()
+    if f64:
+        finite = np.isfinite(g)
+        with np.errstate(all="ignore"):
+            for r in rows.tolist():
+                w = g[lo[r]:hi[r]]
+                dst[r] = (math.fsum(w) if finite[lo[r]:hi[r]].all()
+                          else np.sum(w))
+        return out
+    if op == "sum":
+        run = np.concatenate([[np.uint64(0)],
+                              np.cumsum(g.view(np.uint64))])  # mod 2^64
+        dst.view(np.uint64)[rows] = run[hi[rows]] - run[lo[rows]]
+        return out
+    pick = np.min if op == "min" else np.max
+    for r in rows.tolist():
+        dst[r] = pick(g[lo[r]:hi[r]])
+    return out
+
+
+def pagerank_update(sums: torch.Tensor, old: torch.Tensor,
+                    inv_out: torch.Tensor, damping: float,
+                    dangling: torch.Tensor):
+    """-> (new, contrib, partials f64[1, 2]) in plain torch."""
+    n = sums.numel()
+    new = (1.0 - damping) / max(n, 1) + damping * (sums + dangling / max(n, 1))
+    contrib = new * inv_out
+    partials = torch.stack([(new - old).abs().sum(),
+                            new[inv_out == 0].sum()]).reshape(1, 2)
+    return new, contrib, partials

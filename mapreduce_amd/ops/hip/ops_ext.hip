@@ -19,6 +19,7 @@
 #include "extract_sorted.hip"
 #include "frame.hip"
 #include "gradsum.hip"
+#include "graph.hip"
 #include "group.hip"
 #include "join.hip"
 #include "lex_order.hip"
@@ -1937,6 +1938,100 @@ torch::Tensor frame_reduce(torch::Tensor vals, torch::Tensor lo,
   return frame_apply(vals, lo, hi, t[0], t[1], tree, op, f64);
 }
 
+// ------------------------------------------------ resident-graph propagation
+// caps of the graph kernels: (edges per tile, most blocks of the update pass)
+std::vector<long> graph_caps() { return {GRAPH_TILE, GRAPH_PR_BLOCKS}; }
+
+namespace {
+static_assert(GRAPH_BLOCK == SEG_SCAN_BLOCK,
+              "the graph kernels are launched by SEG_SCAN_LAUNCH");
+
+void check_graph_f64(const torch::Tensor& t, const torch::Tensor& like,
+                     long n, const char* name) {
+  TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
+  TORCH_CHECK(t.scalar_type() == torch::kFloat64, name, " must be float64");
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+  TORCH_CHECK(t.device() == like.device(), name,
+              " must be on the device of sums");
+  TORCH_CHECK(t.numel() == n, name, " must hold ", n, " entries, got ",
+              t.numel());
+}
+}  // namespace
+
+// out[v] = op over e in [offsets[v], offsets[v + 1]) of x[src[e]]; x is the
+// int64 view of an i64 or f64 column of n rows, offsets i64[n + 1], src
+// int32[m].  A src outside [0, n) contributes the identity (0, INT64_MAX,
+// INT64_MIN) and an empty row is the identity.  Three launches behind one
+// fill, no host sync; the inputs are never written.
+torch::Tensor graph_propagate(torch::Tensor offsets, torch::Tensor src,
+                              torch::Tensor x, long op, bool f64) {
+  check_dev_i64(offsets, "offsets");
+  check_dev_i64(x, "x");
+  TORCH_CHECK(src.is_cuda(), "src must be on GPU");
+  TORCH_CHECK(src.scalar_type() == torch::kInt32, "src must be int32");
+  TORCH_CHECK(src.is_contiguous(), "src must be contiguous");
+  TORCH_CHECK(offsets.device() == x.device() && src.device() == x.device(),
+              "offsets, src and x must be on the same device");
+  long n = x.numel(), m = src.numel();
+  TORCH_CHECK(offsets.numel() == n + 1, "offsets must hold ", n + 1,
+              " entries, got ", offsets.numel());
+  TORCH_CHECK(n < (1L << 31) && m < (1L << 31),
+              "graph ops take fewer than 2^31 edges and rows, got ", m,
+              " and ", n);
+  TORCH_CHECK(op >= SEG_SUM && op <= SEG_MAX,
+              "op must be 0 (sum), 1 (min) or 2 (max), got ", op);
+  TORCH_CHECK(op == SEG_SUM || !f64, "graph min / max take int64 values");
+  const i64 ident = op == SEG_SUM ? 0
+                    : op == SEG_MIN ? std::numeric_limits<i64>::max()
+                                    : std::numeric_limits<i64>::min();
+  auto out = torch::full({n}, ident, x.options());
+  if (!n || !m) return out;
+  long ntiles = (m + GRAPH_TILE - 1) / GRAPH_TILE;
+  auto tf = torch::empty({ntiles}, x.options());
+  auto ta = torch::empty({ntiles}, x.options());
+  auto lr = torch::empty({ntiles}, x.options());
+  auto la = torch::empty({ntiles}, x.options());
+  SEG_SCAN_LAUNCH(graph_tile_kernel, ntiles, offsets.data_ptr<i64>(),
+                  src.data_ptr<int>(), u64cp(x), n, m, u64p(out),
+                  tf.data_ptr<i64>(), u64p(ta), lr.data_ptr<i64>(), u64p(la));
+  auto c = seg_scan_carry(tf, ta, op, f64);
+  SEG_SCAN_LAUNCH(graph_lead_kernel, grid_for(ntiles), lr.data_ptr<i64>(),
+                  u64cp(la), c[0].data_ptr<i64>(), u64cp(c[1]), ntiles, n,
+                  u64p(out));
+  return out;
+}
+
+// One PageRank update over n nodes -> (new, contrib, partials f64[blocks, 2]);
+// partials[:, 0] sums to |new - old|_1 and partials[:, 1] to the rank held by
+// nodes whose inv_out is 0.  dangling is a 0-dim (or 1-element) device
+// tensor.  No host sync.
+std::vector<torch::Tensor> pagerank_update(torch::Tensor sums,
+                                           torch::Tensor old,
+                                           torch::Tensor inv_out,
+                                           double damping,
+                                           torch::Tensor dangling) {
+  long n = sums.numel();
+  check_graph_f64(sums, sums, n, "sums");
+  check_graph_f64(old, sums, n, "old");
+  check_graph_f64(inv_out, sums, n, "inv_out");
+  check_graph_f64(dangling, sums, 1, "dangling");
+  TORCH_CHECK(n < (1L << 31), "graph ops take fewer than 2^31 rows, got ", n);
+  auto nw = torch::empty({n}, sums.options());
+  auto contrib = torch::empty({n}, sums.options());
+  long blocks = n ? grid_for(n) : 0;
+  if (blocks > GRAPH_PR_BLOCKS) blocks = GRAPH_PR_BLOCKS;
+  auto partials = torch::empty({blocks, 2}, sums.options());
+  if (blocks)
+    hipLaunchKernelGGL(pagerank_update_kernel, dim3(blocks),
+                       dim3(GRAPH_BLOCK), 0, cur_stream(),
+                       sums.data_ptr<double>(), old.data_ptr<double>(),
+                       inv_out.data_ptr<double>(), n, damping,
+                       dangling.data_ptr<double>(), nw.data_ptr<double>(),
+                       contrib.data_ptr<double>(),
+                       partials.data_ptr<double>());
+  return {nw, contrib, partials};
+}
+
 // Occupancy of the default word-count tokenizer instantiation on the
 // current device, as the runtime sees it (blocks/CU clips the grid; the
 // register count and static LDS are what decide it).
@@ -1975,6 +2070,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "pass 3 of scan_by_key_sorted: the running column");
   m.def("session_flags", &session_flags,
         "1 where a row starts a key or follows a gap in time");
+  m.def("graph_caps", &graph_caps,
+        "(TILE, PR_BLOCKS) of the graph kernels");
+  m.def("graph_propagate", &graph_propagate,
+        "sum / min / max over every row's in-edges of a gathered column");
+  m.def("pagerank_update", &pagerank_update,
+        "one PageRank update -> (new, contrib, partials)");
   m.def("frame_caps", &frame_caps,
         "(TILE, WIN, RTILE) of the frame kernels");
   m.def("frame_bounds", &frame_bounds, py::arg("keys"), py::arg("times"),

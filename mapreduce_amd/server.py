@@ -86,11 +86,12 @@ class Server:
         self.stall_timeout = params.get("stall_timeout", 600.0)
         self.verbose = params.get("verbose", True)
         self.fns = FnSet(fns, self.params["init_args"])
-        # a malformed "group", "window" or "asof" family reducer is
-        # refused here, not mid-task
+        # a malformed "group", "window", "asof" or "graph" family reducer
+        # is refused here, not mid-task
         self.parse_group_reducer(self.fns.reducefn_gpu)
         self.parse_window_reducer(self.fns.reducefn_gpu)
         self.parse_asof_reducer(self.fns.reducefn_gpu)
+        self.parse_graph_reducer(self.fns.reducefn_gpu)
         self.fs = fsmod.router(storage, self.params["path"])
         return self
 
@@ -280,10 +281,64 @@ class Server:
             opts["direction"] = "backward"
         return opts
 
+    # iterative jobs over a resident graph: every key reduces a value
+    # gathered from other keys over its edge list
+    GPU_GRAPH_REDUCERS = ("pagerank", "components")
+
+    @classmethod
+    def parse_graph_reducer(cls, name):
+        """reducefn_gpu of the "graph" family -> {"algo": "pagerank",
+        "damping", "iters", "tol"} or {"algo": "components"}, or None when
+        the name belongs to another family.  "pagerank" alone is d=0.85,
+        iters=100, tol=0; "pagerank:OPT[,OPT...]" takes each of "d=D" (a
+        decimal in [0, 1]), "iters=N" (a decimal integer >= 1) and "tol=T"
+        (a finite decimal >= 0) at most once; "components" takes no option.
+        A malformed name raises ValueError naming the string."""
+        if not isinstance(name, str):
+            return None
+        op, sep, arg = name.partition(":")
+        if op not in cls.GPU_GRAPH_REDUCERS:
+            return None
+        bad = ValueError(
+            f"malformed reducefn_gpu {name!r}: expected 'components' or "
+            "'pagerank[:d=D][,iters=N][,tol=T]' with each option once, a "
+            "decimal 0 <= D <= 1, a decimal integer N >= 1 and a finite "
+            "decimal T >= 0")
+        if op == "components":
+            if sep:
+                raise bad
+            return {"algo": op}
+        opts = {"algo": op, "damping": 0.85, "iters": 100, "tol": 0.0}
+        if not sep:
+            return opts
+        import math
+        import re
+        dec = re.compile(r"(\d+\.?\d*|\.\d+)([eE][+-]?\d+)?")
+        seen = set()
+        for part in arg.split(","):
+            what, eq, txt = part.partition("=")
+            if not eq or what in seen or not txt.isascii():
+                raise bad
+            seen.add(what)
+            if what == "iters":
+                if not txt.isdigit() or int(txt) < 1:
+                    raise bad
+                opts["iters"] = int(txt)
+            elif what in ("d", "tol"):
+                if not dec.fullmatch(txt) or not math.isfinite(float(txt)):
+                    raise bad
+                x = float(txt)
+                if what == "d" and x > 1.0:
+                    raise bad
+                opts["damping" if what == "d" else "tol"] = x
+            else:
+                raise bad
+        return opts
+
     def _gpu_engine_kind(self) -> Optional[str]:
         """Which GPU engine family this task routes to, or None.
 
-        Nine families (one worked example each; README table):
+        Ten families (one worked example each; README table):
           "bytes"   mapfn_gpu + reducefn_gpu="sum" — fused tokenize/
                     combine wordcount engine (examples/wordcount)
           "pairs"   mapfn_gpu_pairs + sum/min/max/minmax — keyed
@@ -306,6 +361,9 @@ class Server:
           "asof"    mapfn_gpu_pairs + join_asof[:backward|forward|nearest,
                     strict,inner,tol=N] — as-of join of two time-ordered
                     relations (examples/asof_quotes)
+          "graph"   mapfn_gpu_pairs + pagerank[:d=D][,iters=N][,tol=T]/
+                    components — iterative jobs over a graph kept resident
+                    on the device (examples/pagerank)
 
         MR_GPU_TIER=off forces host tier; =force routes the GPU data
         path onto the CPU-ops engine (testing without a GPU)."""
@@ -358,6 +416,11 @@ class Server:
             # the as-of join walks the two relations' rows of a key in
             # time order: exact by construction, no property flags
             kind = "asof"
+        elif (callable(fns.mapfn_gpu_pairs)
+              and self.parse_graph_reducer(fns.reducefn_gpu) is not None):
+            # the iteration is defined by the engine, not by a reducer
+            # whose properties could be declared: no property flags
+            kind = "graph"
         elif (callable(fns.mapfn_gpu_pairs)
               and fns.reducefn_gpu in self.GPU_PAIR_REDUCERS
               and fns.associative and fns.commutative
@@ -1316,6 +1379,113 @@ class Server:
         self.print_stats()
 
     # ------------------------------------------------------------ map phase
+    def _loop_gpu_graph(self) -> None:
+        """Resident-graph GPU engine: each map job stages edges as two key
+        columns — mapfn_gpu_pairs(key, value) -> (src, dst) — and the whole
+        iteration runs on the device (gpu/graph.py): the graph is built once
+        as a CSR by destination and every iteration is one
+        ops.graph_propagate pass, so the Python boundary is crossed once
+        per round, not once per iteration.
+
+          "pagerank[:d=D][,iters=N][,tol=T]"
+              finalfn receives (node, [rank]) for every node of either
+              column, after at most N iterations or the first one whose
+              |r' - r|_1 <= T
+          "components"
+              the edges are taken as undirected; finalfn receives
+              (node, [label]), the label being the smallest key of the
+              node's component in u64 order
+
+        finalfn receives the pairs in global u64 key order: rank r emits
+        the r-th contiguous slice of the nodes.  When finalfn returns
+        "loop" and the job signature is unchanged the engine keeps the
+        Graph and continues the ranks for up to N more iterations; a
+        changed signature rebuilds.
+
+        Contract: int64-representable keys."""
+        import torch
+
+        from .gpu import dist as dx
+        from .gpu.graph import GraphJob
+
+        t_start = gettime()
+        rank, world = dx.world_info()
+        device = (torch.device("cuda", torch.cuda.current_device())
+                  if torch.cuda.is_available() else torch.device("cpu"))
+        name = self.fns.reducefn_gpu
+        opts = self.parse_graph_reducer(name)
+        algo = opts["algo"]
+        decode = self.fns.gpu_key_decode or (lambda k: k)
+        gtask = Task(self.coord, key="task_gpu")
+        staged = None  # (job signature, Graph, PageRankResult) — reuse
+        iterations = 0
+
+        while not self.finished:
+            if rank == 0:
+                gtask.create_collection(TASK_STATUS.WAIT, {
+                    "fns": {"engine": f"graph:{algo}"},
+                    "storage": "hbm", "result_ns": "result",
+                }, self.iteration)
+            jobs = self._collect_taskfn_jobs()
+            mine = [kv for i, kv in enumerate(jobs) if i % world == rank]
+            if rank == 0:
+                gtask.set_task_status(TASK_STATUS.MAP)
+            sig = [k for k, _ in mine]
+            if staged is None or staged[0] != sig:
+                parts = [[], []]
+                for k, v in mine:
+                    out = self.fns.mapfn_gpu_pairs(k, v)
+                    if not (isinstance(out, (tuple, list))
+                            and len(out) == 2):
+                        raise ValueError(
+                            "mapfn_gpu_pairs must return (src, dst) under "
+                            f"reducefn_gpu={name!r}; job {k!r} returned "
+                            + (f"a {len(out)}-tuple"
+                               if isinstance(out, (tuple, list))
+                               else type(out).__name__))
+                    for c in range(2):
+                        parts[c].append(torch.as_tensor(out[c],
+                                                        dtype=torch.int64))
+                cols = [torch.cat(p).to(device) if p
+                        else torch.empty(0, dtype=torch.int64, device=device)
+                        for p in parts]
+                graph = GraphJob(device).run(
+                    cols[0], cols[1], symmetric=algo == "components")
+                staged = (sig, graph, None)
+            _, graph, pr = staged
+            if rank == 0:
+                gtask.set_task_status(TASK_STATUS.REDUCE)
+            if algo == "components":
+                vals, rounds = graph.components()
+                iterations += rounds
+            else:
+                before = pr.iterations if pr is not None else 0
+                pr = (graph.pagerank(opts["damping"], opts["iters"],
+                                     opts["tol"]) if pr is None
+                      else pr.more(opts["iters"]))
+                staged = (sig, graph, pr)
+                vals = pr.ranks
+                iterations += pr.iterations - before
+            a, b = graph.owned()
+            pairs = [(decode(int(k)), [v]) for k, v in zip(
+                graph.nodes[a:b].cpu().tolist(), vals[a:b].cpu().tolist())]
+            if rank == 0:
+                gtask.set_task_status(TASK_STATUS.FINISHED)
+            # rank-major concatenation IS global key order: no re-sort
+            reply = self._gpu_finalize_round(pairs, rank, world)
+            if reply == "loop":
+                self.iteration += 1
+                self._log(f"iterative loop -> iteration {self.iteration}")
+            else:
+                self.finished = True
+        self.stats.update({
+            "tier": "gpu", "engine": f"graph:{algo}",
+            "graph_iterations": iterations,
+            "map_failed": 0, "reduce_failed": 0,
+            "total_time": gettime() - t_start,
+        })
+        self.print_stats()
+
     def _prepare_map(self) -> None:
         """server_prepare_map (server.lua:249-276): run taskfn(emit), check
         key uniqueness and value size, insert map job docs, set phase MAP."""
@@ -1498,6 +1668,7 @@ class Server:
                   "group": self._loop_gpu_group,
                   "window": self._loop_gpu_window,
                   "asof": self._loop_gpu_asof,
+                  "graph": self._loop_gpu_graph,
                   "index": self._loop_gpu_index,
                   "gradsum": self._loop_gpu_grads}[kind]
             try:
