@@ -2,7 +2,7 @@
 
 Per step (= one full MapReduce job over the rank's corpus):
 
-  MAP+COMBINE   tokenize_v6 kernel over the coalesced splits: per-block
+  MAP+COMBINE   tokenize_v7 kernel over the coalesced splits: per-block
                 LDS cache tables count the Zipf head in-kernel (the
                 reference's mapfn emit + inline combiner job.lua:83-97);
                 cache misses spill through the wave-chunked allocator,

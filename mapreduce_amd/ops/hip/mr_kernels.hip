@@ -1,11 +1,22 @@
 // MapReduce hot-path kernels for MI355X (gfx950), CDNA4-native.
 //
 // These replace the reference's CPU-Lua hot loops:
-//   K2/K3  tokenize_v6_kernel     — THE production tokenizer: branchless
+//   K2/K3  tokenize_v7_kernel     — THE production tokenizer: branchless
 //          ws-mask scan, chunked register hashing (wordhash64), per-block
 //          LDS cache for the Zipf head, wave-chunked spill allocator for
 //          the tail (template flags add spill-all and fused (word,doc)
-//          composite modes for the inverted index); tokenize_kernel /
+//          composite modes for the inverted index).  It is v6's window:
+//          each lane hashes and probes its words one after the other, in
+//          v6's order.  What differs: the block's next tile is prefetched
+//          into registers during the word loop and written to the ONE LDS
+//          tile buffer after it (two barriers per tile: one right after
+//          the tile's bytes are read into registers, one after the
+//          prefetch is written), and a word's first 8 bytes are extracted
+//          with 32-bit selects + v_alignbyte.  tokenize_v6_kernel differs
+//          only in that it stages the tile in the open (barrier, load,
+//          wait, LDS write, barrier) and extracts every chunk with 64-bit
+//          selects and a funnel shift (MR_TOKENIZE_V6=1, and the sweep /
+//          ablation / bucketed-spill instantiations); tokenize_kernel /
 //          tokenize_count_kernel / tokenize_spill / v5 are earlier
 //          structures kept for tests and recorded A/Bs
 //   K5     bucket_count_kernel    — per-bucket LDS count of the
@@ -975,6 +986,319 @@ __global__ __launch_bounds__(BLOCKN) void tokenize_v6_kernel(
   unsigned long long ws = my_words;
   for (int off = 32; off > 0; off >>= 1) ws += __shfl_down(ws, off, WAVE);
   if (lane_id() == 0 && ws) atomicAdd(nwords, ws);
+}
+
+// ---------------------------------------------------------------------------
+// K2+K5 v7: v6's window (same masks, hashes, cache probes, spill allocator;
+// the same words are cached and spilled) with two changes, both chosen from
+// counters that showed the kernel VALU-bound at 4 waves per SIMD rather than
+// parked (profiles/tokenizer_phases_r07.md):
+//
+//   * The next tile is prefetched into registers.  One window pass covers
+//     the whole tile (TILE_N = 256 x 16) and a thread's 32 bytes + previous
+//     byte are in registers right after the staging barrier, so the tile
+//     buffer is free again at once.  The next tile's global loads (one
+//     16-byte load per thread, the 64-byte halo as one dword on threads
+//     0-15, thread 0's previous byte: no thread makes a second trip) are
+//     issued before the word loop and written to LDS after it; the spill
+//     stores come after that write, so the wait on the prefetch never waits
+//     on stores of its own iteration.  The barrier after the LDS reads is
+//     met by waves that just left the staging barrier together; the one
+//     where waves arrive skewed is still one per tile, and LDS stays at one
+//     tile buffer.  Unaligned text and the last, partial tile are staged by
+//     the plain loop in a cold branch.
+//   * A word's first 8 bytes (all of most words) come from three of the
+//     window's first six dwords, picked by start >> 2 and joined by two
+//     v_alignbyte, instead of 64-bit selects over q0..q3 and a 64-bit funnel
+//     shift: 10 % fewer VALU instructions per job.  Later chunks of longer
+//     words keep v6's form.
+// ---------------------------------------------------------------------------
+#define V7_WAIT_VM0 0x0F70  // s_waitcnt vmcnt(0) alone (gfx9 encoding)
+// threads per block of every v7 launch: one window pass of V7_BLOCK x 16
+// bytes is the tile, and the staging loops stride by it.  The launchers
+// static_assert their block size against it.
+constexpr int V7_BLOCK = 256;
+
+template <int TILE_N>
+__device__ __forceinline__ void v7_stage_plain(u8* tile,
+                                               const u8* __restrict__ text,
+                                               long base, long want,
+                                               bool aligned) {
+  for (int o = threadIdx.x * 16; o < want; o += V7_BLOCK * 16) {
+    if (aligned && o + 16 <= want) {
+      *(uint4*)&tile[o] = *(const uint4*)&text[base + o];
+    } else {
+      for (int b = 0; b < 16 && o + b < want; ++b)
+        tile[o + b] = text[base + o + b];
+    }
+  }
+}
+
+template <int CACHE_N, bool GPOS, bool SPILL_ALL = false,
+          bool COMPOSITE = false, int SCHUNK = 512>
+// 5 waves per SIMD asked for where the LDS admits 5 blocks: 96 VGPRs, as v6
+__global__ __launch_bounds__(V7_BLOCK, GPOS || SPILL_ALL ? 5 : 3)
+void tokenize_v7_kernel(
+    const u8* __restrict__ text, long n, u64 pos_base,
+    u64* __restrict__ tkeys, i64* __restrict__ tvals, u64* __restrict__ texm,
+    u64 cap_mask, u64* __restrict__ out_hash, u64* __restrict__ out_pos,
+    unsigned long long* __restrict__ spill_counter, long spill_cap,
+    unsigned long long* __restrict__ nwords, u64* __restrict__ cpos_g,
+    const i64* __restrict__ split_off = nullptr, int nsplit_off = 0,
+    long doc_base = 0) {
+  constexpr int TILE_N = V7_BLOCK * TOK_BYTES;  // one window pass per tile
+  __shared__ __align__(16) u8 tile[TILE_N + TOK_HALO];
+  __shared__ u64 ckeys[CACHE_N];
+  __shared__ u64 cpos_l[GPOS ? 1 : CACHE_N];
+  __shared__ u32 ccnt[CACHE_N];
+  u64* cpos = GPOS ? &cpos_g[(u64)blockIdx.x * CACHE_N] : cpos_l;
+  for (int s = threadIdx.x; s < CACHE_N; s += blockDim.x) {
+    ckeys[s] = HT_EMPTY;
+    ccnt[s] = 0;
+  }
+  const int tid = threadIdx.x;
+  const int lane = tid & (WAVE - 1);
+  unsigned long long my_words = 0;
+  constexpr int SPILL_CHUNK = SCHUNK;
+  long wchunk = -1;
+  int wleft = 0;
+  const long tile0 = (long)blockIdx.x * TILE_N;
+  const long tstride = (long)gridDim.x * TILE_N;
+  // uniform per launch: base and o are multiples of 16
+  const bool aligned = (((uintptr_t)text) & 15) == 0;
+  if (tile0 < n) {
+    long avail0 = n - tile0;
+    v7_stage_plain<TILE_N>(tile, text, tile0,
+                           avail0 < TILE_N + TOK_HALO ? avail0
+                                                      : TILE_N + TOK_HALO,
+                           aligned);
+  }
+  const long my0 = (long)tid * TOK_BYTES;
+  // the byte before the tile (thread 0's previous byte) travels with the
+  // prefetch in a register: a load of it inside the window would make wave
+  // 0 wait for the whole prefetch (loads return in order)
+  u32 pb_cur = (tid == 0 && tile0 > 0 && tile0 < n) ? text[tile0 - 1] : 0x20;
+  // nothing is in flight when the loop is entered: the compiler's wait
+  // placement then sees a register written by a pending load only on paths
+  // where it is one, and keeps the top of the loop free of vmcnt waits.
+  // This only steers the compiler and a later one may place its waits
+  // differently.  To check that it still helps, read the ISA of the
+  // default instantiation (hipcc -S --offload-arch=gfx950 -O3): inside
+  // the tile loop there must be no s_waitcnt vmcnt between the
+  // global_load_dwordx4 / global_load_dword of the prefetch and the second
+  // s_barrier, and none after it before the word loop's first
+  // global_load_ubyte (the long-word scan).  Without this line there were
+  // three vmcnt(0) there and the prefetch was waited for at once.
+  __builtin_amdgcn_s_waitcnt(V7_WAIT_VM0);
+  for (long base = tile0; base < n; base += tstride) {
+    const long avail = n - base;
+    const long want = avail < TILE_N + TOK_HALO ? avail : TILE_N + TOK_HALO;
+    // next tile of this block: prefetched when it is a full tile + halo of
+    // 16-byte-aligned text, staged by the plain loop otherwise
+    const long nbase = base + tstride;
+    const bool pf_fast = aligned && nbase + TILE_N + TOK_HALO <= n;
+    uint4 pf = uint4{0, 0, 0, 0};
+    u32 ph = 0;
+    u32 pb_next = 0x20;
+    if (tid == 0 && nbase < n) pb_next = text[nbase - 1];
+    if (pf_fast) {
+      pf = *(const uint4*)&text[nbase + my0];
+      if (tid < TOK_HALO / 4) ph = *(const u32*)&text[nbase + TILE_N + tid * 4];
+    }
+    __syncthreads();
+    // whole wave stays in the loop (the spill wave-scan below needs every
+    // lane present); out-of-range lanes just contribute ns = 0
+    const bool wactive = my0 < avail;
+    const uint4 va = wactive ? *(const uint4*)&tile[my0] : uint4{0, 0, 0, 0};
+    const uint4 vb = wactive ? *(const uint4*)&tile[my0 + 16] : uint4{0, 0, 0, 0};
+    u32 prevb = (base + my0 == 0)
+                    ? 1u
+                    : (wactive ? (u32)is_ws(my0 ? tile[my0 - 1]
+                                                : (u8)pb_cur) : 1u);
+    __syncthreads();  // every thread holds its bytes: the tile buffer
+                      // may be overwritten
+    const u64 q0 = (u64)va.x | ((u64)va.y << 32);
+    const u64 q1 = (u64)va.z | ((u64)va.w << 32);
+    const u64 q2 = (u64)vb.x | ((u64)vb.y << 32);
+    const u64 q3 = (u64)vb.z | ((u64)vb.w << 32);
+    u32 m32 = ws_mask8(q0) | (ws_mask8(q1) << 8) |
+              (ws_mask8(q2) << 16) | (ws_mask8(q3) << 24);
+    // bytes at/after `want` count as whitespace (stale stage data)
+    long lim32 = want - my0;
+    if (lim32 < 32)
+      m32 |= (lim32 <= 0) ? 0xFFFFFFFFu : ~((1u << lim32) - 1);
+    u32 sm = wactive ? (~m32 & ((m32 << 1) | prevb) & 0xFFFFu) : 0u;
+    long limw = avail - my0;  // starts must be real data bytes
+    if (limw < 16) sm &= (limw <= 0) ? 0u : ((1u << limw) - 1);
+    my_words += __popc(sm);
+    // compile-time slot indices keep sh_[] in registers (see v6); only the
+    // keys are buffered, positions are rebuilt at the store (v6_spill_pos)
+    u64 sh_[8];
+    const u32 sm0 = sm;
+    u32 long_len = 0;
+    const u64 wpos0 = pos_base + (u64)(base + my0);
+    u32 miss_mask = 0;
+    // ---- v6's word loop
+    #pragma unroll
+    for (int wi = 0; wi < 8; ++wi) {
+      if (!sm) break;
+      int s = __ffs(sm) - 1;
+      sm &= sm - 1;
+      u32 t = m32 >> s;
+      u64 h = FNV64_OFFSET;
+      u32 len;
+      if (t) {
+        len = (u32)(__ffs(t) - 1);  // bit s is clear, so len >= 1
+        {
+          // bytes s..s+7 (s < 16): three of the window's first six dwords
+          // picked by s >> 2, joined by two byte-aligns
+          const int di = s >> 2;
+          const u32 bsh = (u32)s & 3u;
+          u32 a0 = (di & 2) ? ((di & 1) ? va.w : va.z) : ((di & 1) ? va.y : va.x);
+          u32 a1 = (di & 2) ? ((di & 1) ? vb.x : va.w) : ((di & 1) ? va.z : va.y);
+          u32 a2 = (di & 2) ? ((di & 1) ? vb.y : vb.x) : ((di & 1) ? va.w : va.z);
+          u64 w = (u64)__builtin_amdgcn_alignbyte(a1, a0, bsh) |
+                  ((u64)__builtin_amdgcn_alignbyte(a2, a1, bsh) << 32);
+          u32 nb = len < 8 ? len : 8;
+          w &= ~(u64)0 >> (64 - 8 * nb);
+          h = whash_chunk(h, w);
+        }
+        for (u32 c = 8; c < len; c += 8) {
+          int j0 = s + (int)c;
+          int qi = j0 >> 3;
+          u64 lo = (qi & 2) ? ((qi & 1) ? q3 : q2) : ((qi & 1) ? q1 : q0);
+          u64 hi = (qi >= 3) ? 0 : ((qi & 2) ? q3 : ((qi & 1) ? q2 : q1));
+          int sh2 = 8 * (j0 & 7);
+          u64 w = sh2 ? ((lo >> sh2) | (hi << (64 - sh2))) : lo;
+          u32 rem = len - c;
+          if (rem < 8) w &= (((u64)1 << (8 * rem)) - 1);
+          h = whash_chunk(h, w);
+        }
+        h = whash_fin(h, len);
+      } else {
+        // word longer than the 32-byte window: scan from global
+        long g = base + my0 + s;
+        u64 chunk = 0;
+        int cb = 0;
+        long wlen = 0;
+        while (g < n && !is_ws(text[g])) {
+          chunk |= (u64)text[g] << (8 * cb);
+          if (++cb == 8) {
+            h = whash_chunk(h, chunk);
+            chunk = 0;
+            cb = 0;
+          }
+          ++g;
+          ++wlen;
+        }
+        if (cb) h = whash_chunk(h, chunk);
+        h = whash_fin(h, (u64)wlen);
+        len = (u32)(wlen > 0xFFFF ? 0xFFFF : wlen);
+        long_len = len;
+      }
+      if (COMPOSITE) {
+        i64 byte = (i64)(pos_base + (u64)(base + my0 + s));
+        int doc = ub_minus1(split_off, nsplit_off, byte);
+        h ^= splitmix64_dev((u64)(doc + doc_base));
+      }
+      u64 k = remap_key(h);
+      sh_[wi] = k;
+      if (SPILL_ALL) {
+        miss_mask |= 1u << wi;
+        continue;
+      }
+      // v6's probe, one word at a time
+      u64 p = ((pos_base + (u64)(base + my0 + s)) << 16) | (u64)len;
+      u32 slot = (u32)((k ^ (k >> 32)) & (CACHE_N - 1));
+      bool done = false;
+      for (int pr = 0; pr < TOK_PROBE; ++pr) {
+        u64 cur2 = ckeys[slot];
+        if (cur2 == k) {
+          atomicAdd(&ccnt[slot], 1u);
+          done = true;
+          break;
+        }
+        if (cur2 == HT_EMPTY) {
+          u64 prevk = atomicCAS((unsigned long long*)&ckeys[slot],
+                                (unsigned long long)HT_EMPTY,
+                                (unsigned long long)k);
+          if (prevk == HT_EMPTY) cpos[slot] = p;
+          if (prevk == HT_EMPTY || prevk == k) {
+            atomicAdd(&ccnt[slot], 1u);
+            done = true;
+            break;
+          }
+        }
+        slot = (slot + 1) & (CACHE_N - 1);
+      }
+      if (!done) miss_mask |= 1u << wi;
+    }
+    // ---- the prefetched tile goes to LDS before this window's spill
+    // stores are issued (the wait above them is then for loads only)
+    if (nbase < n) {
+      if (pf_fast) {
+        *(uint4*)&tile[my0] = pf;
+        if (tid < TOK_HALO / 4) *(u32*)&tile[TILE_N + tid * 4] = ph;
+      } else {
+        long navail = n - nbase;
+        v7_stage_plain<TILE_N>(tile, text, nbase,
+                               navail < TILE_N + TOK_HALO ? navail
+                                                          : TILE_N + TOK_HALO,
+                               aligned);
+      }
+    }
+    pb_cur = pb_next;  // here, not at its load: the copy waits for it
+    // ---- spill phase (v6's): wave scan, chunk reservation, stores
+    {
+      u32 my_ns = (u32)__popc(miss_mask);
+      u32 incl = my_ns;
+      #pragma unroll
+      for (int off = 1; off < WAVE; off <<= 1) {
+        u32 x = __shfl_up(incl, off, WAVE);
+        if (lane >= off) incl += x;
+      }
+      u32 wave_total = __shfl(incl, WAVE - 1, WAVE);
+      if (wave_total && (int)wave_total > wleft) {
+        for (int i = lane; i < wleft; i += WAVE)
+          if (wchunk + i < spill_cap) out_hash[wchunk + i] = HT_EMPTY;
+        int grab = (int)wave_total > SPILL_CHUNK ? (int)wave_total
+                                                 : SPILL_CHUNK;
+        unsigned long long nb = 0;
+        if (lane == 0)
+          nb = atomicAdd(spill_counter, (unsigned long long)grab);
+        wchunk = (long)__shfl(nb, 0, WAVE);
+        wleft = grab;
+      }
+      long o = wchunk + (long)(incl - my_ns);
+      if (wave_total) {
+        wchunk += wave_total;
+        wleft -= (int)wave_total;
+      }
+      u32 smw = sm0;
+      #pragma unroll
+      for (int wi = 0; wi < 8; ++wi) {
+        if (miss_mask & (1u << wi)) {
+          u64 p = v6_spill_pos(wpos0, smw, m32, long_len);
+          if (o < spill_cap) {
+            out_hash[o] = sh_[wi];
+            out_pos[o] = p;
+          }
+          ++o;
+        }
+        smw &= smw - 1;
+      }
+    }
+  }
+  // retire this wave's final spill-chunk tail
+  for (int i = lane; i < wleft; i += WAVE)
+    if (wchunk + i < spill_cap) out_hash[wchunk + i] = HT_EMPTY;
+  __syncthreads();
+  for (int s = tid; s < CACHE_N; s += blockDim.x)
+    if (ckeys[s] != HT_EMPTY && ccnt[s])
+      ht_add(ckeys[s], cpos[s], (i64)ccnt[s], tkeys, tvals, texm, cap_mask);
+  unsigned long long ws = my_words;
+  for (int off = 32; off > 0; off >>= 1) ws += __shfl_down(ws, off, WAVE);
+  if (lane == 0 && ws) atomicAdd(nwords, ws);
 }
 
 // Ablation copy of the tokenize kernel (diagnosis only — §5.4 rule 8:

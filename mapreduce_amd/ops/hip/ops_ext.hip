@@ -132,6 +132,37 @@ bool radix_v2_forced() {
   return f == 1;
 }
 
+// The tokenizer body of the cached word-count, spill-all and composite
+// launches is tokenize_v7_kernel (next tile prefetched into registers, a
+// word's first chunk extracted with byte-aligns); MR_TOKENIZE_V6=1, read
+// once per process, selects its predecessor for A/B inside one session.
+// Both cache and spill the same words, so results are the same.
+bool tok_v6_forced() {
+  static int f = -1;
+  if (f < 0) {
+    const char* v = getenv("MR_TOKENIZE_V6");
+    f = (v && v[0] == '1') ? 1 : 0;
+  }
+  return f == 1;
+}
+
+static_assert(kBlock == V7_BLOCK, "v7 launches use kBlock threads");
+
+// Which body the most recent v6/v7 tokenizer launch of this process
+// dispatched ("v7", "v6", or "none" before the first): set where the kernel
+// pointer is chosen, so tests see the launchers' decision itself.
+const char* g_tok_last_body = "none";
+
+// max_blocks of the tokenizer bindings: 0 keeps the launcher's grid,
+// anything else caps it (clamped to [1, kMaxBlocks]) so that a small input
+// can make one block walk several tiles.
+long tok_cap_blocks(long blocks, long max_blocks) {
+  if (max_blocks == 0) return blocks;
+  long m = max_blocks < 1 ? 1 : (max_blocks > kMaxBlocks ? kMaxBlocks
+                                                         : max_blocks);
+  return blocks < m ? blocks : m;
+}
+
 // the staged scatter this process runs, for one set of template arguments.
 // LATE (v3 only) = fetch the payload at staging time instead of up front:
 // faster for the full sorts (TeraSort's 671M-record passes: 8.7 against
@@ -257,7 +288,8 @@ void tokenize_count(torch::Tensor text, long pos_base, torch::Tensor tkeys,
 // inverted-index tokenize path; replaces tokenize_spill's per-window
 // shared-counter atomics (cross-XCD contention, see tokenize_v6 note).
 std::vector<torch::Tensor> tokenize_spill_v2(torch::Tensor text,
-                                             long pos_base, long cap) {
+                                             long pos_base, long cap,
+                                             long max_blocks) {
   TORCH_CHECK(text.is_cuda() && text.scalar_type() == torch::kUInt8 &&
               text.is_contiguous(), "text must be contiguous u8 on GPU");
   long n = text.numel();
@@ -276,8 +308,12 @@ std::vector<torch::Tensor> tokenize_spill_v2(torch::Tensor text,
     // cache to warm or flush, and the inverted index measured 8.05-8.08
     // ms/job on the one-round grid vs 8.03-8.06 on this one (parent
     // 8.02-8.07; profiles/tokenizer_occupancy_r04.md)
-    hipLaunchKernelGGL((tokenize_v6_kernel<16, false, 4096, 0, true>),
-                       dim3(grid_for(n, TOK_BYTES)), dim3(kBlock), 0,
+    auto kfn = tokenize_v7_kernel<16, false, true>;
+    if (tok_v6_forced()) kfn = tokenize_v6_kernel<16, false, 4096, 0, true>;
+    g_tok_last_body = tok_v6_forced() ? "v6" : "v7";
+    hipLaunchKernelGGL(kfn,
+                       dim3(tok_cap_blocks(grid_for(n, TOK_BYTES), max_blocks)),
+                       dim3(kBlock), 0,
                        cur_stream(), text.data_ptr<u8>(), n, (u64)pos_base,
                        u64p(dummy), dummy.data_ptr<i64>(), nullptr,
                        (u64)15, u64p(out_hash), u64p(out_pos),
@@ -291,7 +327,7 @@ std::vector<torch::Tensor> tokenize_spill_v2(torch::Tensor text,
 
 std::vector<torch::Tensor> tokenize_spill_composite(
     torch::Tensor text, long pos_base, long cap, torch::Tensor split_off,
-    long doc_base) {
+    long doc_base, long max_blocks) {
   TORCH_CHECK(text.is_cuda() && text.scalar_type() == torch::kUInt8 &&
               text.is_contiguous(), "text must be contiguous u8 on GPU");
   check_dev_i64(split_off, "split_off");
@@ -303,8 +339,13 @@ std::vector<torch::Tensor> tokenize_spill_composite(
   auto nwords = torch::zeros({1}, opts);
   if (n) {
     auto dummy = torch::empty({16}, opts);
-    hipLaunchKernelGGL((tokenize_v6_kernel<16, false, 4096, 0, true, true>),
-                       dim3(grid_for(n, TOK_BYTES)), dim3(kBlock), 0,
+    auto kfn = tokenize_v7_kernel<16, false, true, true>;
+    if (tok_v6_forced())
+      kfn = tokenize_v6_kernel<16, false, 4096, 0, true, true>;
+    g_tok_last_body = tok_v6_forced() ? "v6" : "v7";
+    hipLaunchKernelGGL(kfn,
+                       dim3(tok_cap_blocks(grid_for(n, TOK_BYTES), max_blocks)),
+                       dim3(kBlock), 0,
                        cur_stream(), text.data_ptr<u8>(), n, (u64)pos_base,
                        u64p(dummy), dummy.data_ptr<i64>(), nullptr,
                        (u64)15, u64p(out_hash), u64p(out_pos),
@@ -327,7 +368,8 @@ void tokenize_cache_spill_composite(
     torch::Tensor text, long pos_base, torch::Tensor tkeys,
     torch::Tensor tvals, torch::Tensor texm, long spill_cap,
     torch::Tensor nwords, torch::Tensor out_hash, torch::Tensor out_pos,
-    torch::Tensor counter, torch::Tensor split_off, long doc_base) {
+    torch::Tensor counter, torch::Tensor split_off, long doc_base,
+    long max_blocks) {
   TORCH_CHECK(text.is_cuda() && text.scalar_type() == torch::kUInt8 &&
               text.is_contiguous(), "text must be contiguous u8 on GPU");
   check_dev_i64(split_off, "split_off");
@@ -337,9 +379,11 @@ void tokenize_cache_spill_composite(
   TORCH_CHECK(out_hash.numel() >= spill_cap && out_pos.numel() >= spill_cap,
               "spill arrays too small");
   if (!n) return;
-  auto kfn =
-      tokenize_v6_kernel<2048, true, 4096, 0, false, true, 2048, 0, 256>;
-  long blocks = tok_grid(kfn, kBlock, n, 4096);
+  auto kfn = tokenize_v7_kernel<2048, true, false, true, 2048>;
+  if (tok_v6_forced())
+    kfn = tokenize_v6_kernel<2048, true, 4096, 0, false, true, 2048, 0, 256>;
+  g_tok_last_body = tok_v6_forced() ? "v6" : "v7";
+  long blocks = tok_cap_blocks(tok_grid(kfn, kBlock, n, 4096), max_blocks);
   static torch::Tensor cpos_gc;  // persistent GPOS side-buffer
   long need = blocks * 2048;
   if (!cpos_gc.defined() || cpos_gc.numel() < need ||
@@ -385,7 +429,7 @@ void tokenize_cache_spill(
     torch::Tensor text, long pos_base, torch::Tensor tkeys,
     torch::Tensor tvals, torch::Tensor texm, long spill_cap,
     torch::Tensor nwords, torch::Tensor out_hash, torch::Tensor out_pos,
-    torch::Tensor counter) {
+    torch::Tensor counter, long max_blocks) {
   TORCH_CHECK(text.is_cuda() && text.scalar_type() == torch::kUInt8 &&
               text.is_contiguous(), "text must be contiguous u8 on GPU");
   long n = text.numel();
@@ -394,9 +438,11 @@ void tokenize_cache_spill(
   TORCH_CHECK(out_hash.numel() >= spill_cap && out_pos.numel() >= spill_cap,
               "spill arrays too small");
   if (n) {
-    // Default v6: branchless ws-mask scan + register-funnel hashing in
-    // v4's single-phase structure — measured 5.10 vs 6.25 ms/step (+23%)
-    // over v4's per-byte scan.  Recorded alternatives: MR_TOKENIZE_V4=1
+    // Default v7 (v6 with the next tile prefetched into registers and a
+    // cheaper first-chunk extract; MR_TOKENIZE_V6=1 for v6).  v6: branchless
+    // ws-mask scan + register-funnel hashing in v4's single-phase structure
+    // — measured 5.10 vs 6.25 ms/step (+23%) over v4's per-byte scan.
+    // Recorded alternatives: MR_TOKENIZE_V4=1
     // (per-byte scan loop), MR_TOKENIZE_V5=1 (word-list restructure,
     // measured 2x SLOWER: extra barriers + LDS footprint outweigh lane
     // balance at this grain).
@@ -423,7 +469,8 @@ void tokenize_cache_spill(
       int schunk = sc ? atoi(sc) : 2048;
       // MR_TOK_BLOCK=512: 8 KB tile in ONE window pass (same per-thread
       // geometry as 256/4096) — +2 KB LDS for 2x waves/block, occupancy
-      // probe for the 68%-wait tokenizer
+      // probe from when the tokenizer was read as wait-bound (its VALU
+      // is ~74 % busy across the 4 waves of a SIMD: round 7)
       const char* tb = getenv("MR_TOK_BLOCK");
       int blockn = (tb && atoi(tb) == 512) ? 512 : 256;
       if (blockn == 512) tsz = 8192;
@@ -447,7 +494,16 @@ void tokenize_cache_spill(
       else if (cache == 1024) kfn = tokenize_v6_kernel<1024, false, 4096>;
       else if (schunk == 128)
         kfn = tokenize_v6_kernel<2048, false, 4096, 0, false, false, 128>;
-      long blocks = tok_grid(kfn, blockn, n, tsz);
+      // the two shapes the job runs (every knob at its default, GPOS on
+      // or off) take the v7 body; the sweep shapes above stay v6 bodies
+      g_tok_last_body = "v6";
+      if (!tok_v6_forced() && cache == 2048 && tsz == 4096 &&
+          schunk == 2048 && blockn == V7_BLOCK) {
+        if (gpos) kfn = tokenize_v7_kernel<2048, true, false, false, 2048>;
+        else kfn = tokenize_v7_kernel<2048, false>;
+        g_tok_last_body = "v7";
+      }
+      long blocks = tok_cap_blocks(tok_grid(kfn, blockn, n, tsz), max_blocks);
       static torch::Tensor cpos_g;  // persistent side-buffer (GPOS only)
       u64* cpg = nullptr;
       if (gpos) {
@@ -2034,9 +2090,12 @@ std::vector<torch::Tensor> pagerank_update(torch::Tensor sums,
 
 // Occupancy of the default word-count tokenizer instantiation on the
 // current device, as the runtime sees it (blocks/CU clips the grid; the
-// register count and static LDS are what decide it).
+// register count and static LDS are what decide it), and which body this
+// process runs ("v7", or "v6" under MR_TOKENIZE_V6=1).
 py::dict tokenizer_occupancy() {
-  auto kfn = tokenize_v6_kernel<2048, true, 4096, 0, false, false, 2048>;
+  auto kfn = tokenize_v7_kernel<2048, true, false, false, 2048>;
+  if (tok_v6_forced())
+    kfn = tokenize_v6_kernel<2048, true, 4096, 0, false, false, 2048>;
   TokOccupancy o = tok_occupancy(reinterpret_cast<const void*>(kfn), kBlock);
   hipFuncAttributes fa;
   C10_HIP_CHECK(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kfn)));
@@ -2045,10 +2104,15 @@ py::dict tokenizer_occupancy() {
   d["cus"] = o.cus;
   d["num_regs"] = fa.numRegs;
   d["lds_bytes"] = (long)fa.sharedSizeBytes;
+  d["body"] = tok_v6_forced() ? "v6" : "v7";
   return d;
 }
 
+std::string tokenizer_last_body() { return g_tok_last_body; }
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("tokenizer_last_body", &tokenizer_last_body,
+        "body of the last v6/v7 tokenizer launch: v7, v6 or none");
   m.def("group_caps", &group_caps, "(TILE, QMAX) of the group kernels");
   m.def("group_rank_max", &group_rank_max,
         "longest segment of the tile kernel's rank-counting pass");
@@ -2132,14 +2196,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("tokenize_count", &tokenize_count,
         "fused tokenize + hash-table count");
   m.def("tokenize_spill_composite", &tokenize_spill_composite,
+        py::arg("text"), py::arg("pos_base"), py::arg("cap"),
+        py::arg("split_off"), py::arg("doc_base"), py::arg("max_blocks") = 0,
         "spill-all with fused (word,doc) composite keys");
   m.def("tokenize_cache_spill_composite", &tokenize_cache_spill_composite,
+        py::arg("text"), py::arg("pos_base"), py::arg("tkeys"),
+        py::arg("tvals"), py::arg("texm"), py::arg("spill_cap"),
+        py::arg("nwords"), py::arg("out_hash"), py::arg("out_pos"),
+        py::arg("counter"), py::arg("split_off"), py::arg("doc_base"),
+        py::arg("max_blocks") = 0,
         "composite keys with the LDS cache (misses spill)");
-  m.def("tokenize_spill_v2", &tokenize_spill_v2,
+  m.def("tokenize_spill_v2", &tokenize_spill_v2, py::arg("text"),
+        py::arg("pos_base"), py::arg("cap"), py::arg("max_blocks") = 0,
         "spill-all tokenizer (chunk-padded; filter HT_EMPTY)");
   m.def("tokenize_spill", &tokenize_spill,
         "tokenize -> compact (hash,pos) arrays");
-  m.def("tokenize_cache_spill", &tokenize_cache_spill,
+  m.def("tokenize_cache_spill", &tokenize_cache_spill, py::arg("text"),
+        py::arg("pos_base"), py::arg("tkeys"), py::arg("tvals"),
+        py::arg("texm"), py::arg("spill_cap"), py::arg("nwords"),
+        py::arg("out_hash"), py::arg("out_pos"), py::arg("counter"),
+        py::arg("max_blocks") = 0,
         "tokenize; LDS cache counts the head, misses spill");
   m.def("tokenize_cache_spill_bucketed", &tokenize_cache_spill_bucketed,
         "tokenize; misses spill directly into per-top-byte-bucket regions");

@@ -71,7 +71,7 @@ def fnv1a64(data: Any) -> int:
 def wordhash64(data: Any) -> int:
     """Chunked 64-bit word hash: one xor-multiply per 8 little-endian
     bytes (zero-padded) + a length fold.  The GPU engine's dictionary hash
-    (tokenize_v6): 6x fewer dependent multiplies than byte-serial FNV-1a
+    (tokenize_v6 / v7): 6x fewer dependent multiplies than byte-serial FNV-1a
     and provably collision-free for distinct words of <= 8 bytes (the
     multiply by an odd prime is bijective).  Must match whash_* in
     ops/hip/common.h."""
