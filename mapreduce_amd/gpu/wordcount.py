@@ -96,8 +96,7 @@ class WordCountResult:
         else:
             raise ValueError(
                 f"results keyed with {self.hash_kind!r} do not support "
-                "hash lookups (archived MR_TOKENIZE_V4/V5 tokenizers "
-                "predate the wordhash64 migration)")
+                "hash lookups")
         return k - (1 << 64) if k >= (1 << 63) else k
 
     def count_of(self, word) -> int:
@@ -246,7 +245,7 @@ class WordCountResult:
 
 class WordCountJob:
     """mode:
-      "streaming" (GPU default) — tokenize_spill -> top-byte radix
+      "streaming" (GPU default) — tokenize_cache_spill -> top-byte radix
         bucketize -> per-bucket LDS count (all per-word atomics in LDS);
       "fused" — tokenize straight into the global hash table (slower on
         Zipf text: per-word probes are L2-latency-bound; kept for A/B and
@@ -321,41 +320,11 @@ class WordCountJob:
         self._events = []
         self._mark("start")
         if self.mode == "streaming":
-            import os
             opts = dict(dtype=torch.int64, device=self.device)
-            # bucketed direct spill (MR_TOK_BSPILL=1): the tokenizer lands
-            # misses straight into 256 per-top-byte-bucket regions,
-            # removing the radix_pass(56) bucketize and all pad entries.
-            # MEASURED 5x SLOWER (11.1 vs 2.09 ms/step): one reservation
-            # atomic per distinct bucket per wave-window exposes a full
-            # L2-atomic round trip per miss-group (~430 serial stalls per
-            # wave), exactly the latency the 512-entry chunked allocator
-            # amortizes away.  Kept env-gated for the record; default OFF.
-            self._bspill = (
-                self.device.type == "cuda"
-                and os.environ.get("MR_TOK_BSPILL", "0") == "1"
-                and os.environ.get("MR_TOK_CACHE", "2048") == "2048"
-                and os.environ.get("MR_TOK_TILE", "4096") == "4096"
-                and os.environ.get("MR_TOKENIZE_V4", "0") != "1"
-                and os.environ.get("MR_TOKENIZE_V5", "0") != "1")
-            if self._bspill:
-                # same total footprint as the chunked layout; uniform hash
-                # top byte spreads misses, ~30x headroom per bucket, loud
-                # overflow check in finish_map
-                bcap = max(4096, (text.numel() // 2 + 16) // 256 + 2048)
-                self._spill_h = torch.empty(256 * bcap, **opts)
-                self._spill_p = torch.empty(256 * bcap, **opts)
-                self._spill_c = torch.zeros(256, **opts)
-                self._spill_bcap = bcap
-                return
             # + slack for the wave-chunked spill allocator's padded chunk
-            # tails (<= 2048 blocks x 4 waves x one chunk each)
-            try:
-                schunk = int(os.environ.get("MR_SPILL_CHUNK", "2048"))
-            except ValueError:
-                schunk = 2048
+            # tails (<= 2048 blocks x 4 waves x one 2048-entry chunk each)
             cap = (text.numel() // 2 + 16
-                   + max(1, expected_launches) * 2048 * 4 * max(schunk, 512))
+                   + max(1, expected_launches) * 2048 * 4 * 2048)
             self._spill_h = torch.empty(cap, **opts)
             self._spill_p = torch.empty(cap, **opts)
             self._spill_c = torch.zeros(1, **opts)
@@ -366,16 +335,10 @@ class WordCountJob:
         Streaming mode appends cache misses to the shared spill arrays
         (atomic counter append composes across launches)."""
         if self.mode == "streaming":
-            if self._bspill:
-                ops.ext().tokenize_cache_spill_bucketed(
-                    self._text[s:e], s, self.table.tkeys, self.table.tvals,
-                    self.table.texm, self._spill_bcap, self._nwords,
-                    self._spill_h, self._spill_p, self._spill_c)
-            else:
-                ops.ext().tokenize_cache_spill(
-                    self._text[s:e], s, self.table.tkeys, self.table.tvals,
-                    self.table.texm, self._spill_cap, self._nwords,
-                    self._spill_h, self._spill_p, self._spill_c)
+            ops.ext().tokenize_cache_spill(
+                self._text[s:e], s, self.table.tkeys, self.table.tvals,
+                self.table.texm, self._spill_cap, self._nwords,
+                self._spill_h, self._spill_p, self._spill_c)
         else:
             self.table.tokenize_count(self._text[s:e], s, self._nwords)
 
@@ -392,23 +355,6 @@ class WordCountJob:
             import os
             slices = int(os.environ.get("MR_BUCKET_SLICES",
                                         DEFAULT_BUCKET_SLICES))
-            if self._bspill:
-                # misses are already bucket-partitioned in per-bucket
-                # regions; counters hold exact per-bucket lengths
-                cnts = self._spill_c.cpu()
-                n = int(self._nwords.item())
-                mx = int(cnts.max().item())
-                if mx > self._spill_bcap:
-                    raise RuntimeError(
-                        f"bucketed spill overflow: {mx} reserved > "
-                        f"per-bucket cap {self._spill_bcap}")
-                if int(cnts.sum().item()):
-                    ops.ext().bucket_count(
-                        self._spill_h, self._spill_p, self._spill_c, 256,
-                        slices, self.table.tkeys, self.table.tvals,
-                        self.table.texm, self._spill_bcap, 1024)
-                self._spill_h = self._spill_p = None
-                return n
             # ONE packed D2H for both scalars (each .item() is a full
             # stream sync)
             both = torch.cat([self._spill_c, self._nwords]).cpu()
@@ -696,12 +642,7 @@ class WordCountJob:
 
         self._mark("shuffle_reduce")
         self._collect_timing()
-        import os
-        legacy = (dev.type == "cuda"
-                  and (os.environ.get("MR_TOKENIZE_V4") == "1"
-                       or os.environ.get("MR_TOKENIZE_V5") == "1"))
         return WordCountResult(
             keys=fk, counts=fv, pos=fp, blob_src=blob_src, nwords=nwords,
-            hash_kind=("legacy-fnv" if legacy else
-                       "wordhash64" if dev.type == "cuda" else "fnv1a64"),
+            hash_kind="wordhash64" if dev.type == "cuda" else "fnv1a64",
             **(cache or {}))

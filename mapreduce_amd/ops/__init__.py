@@ -26,7 +26,33 @@ def have_ext() -> bool:
     return _ext is not None
 
 
+# Tokenizer switches whose kernels were removed.  Setting one used to pick
+# another kernel; an A/B that silently compares a build with itself is worse
+# than an error, so they fail loudly.
+RETIRED_SWITCHES = (
+    "MR_TOKENIZE_V4", "MR_TOKENIZE_V5", "MR_TOK_BSPILL", "MR_TOK_CACHE",
+    "MR_TOK_TILE", "MR_TOK_BLOCK", "MR_SPILL_CHUNK")
+
+
+def check_retired_switches(environ=None) -> None:
+    env = os.environ if environ is None else environ
+    for name in RETIRED_SWITCHES:
+        if name in env:
+            raise RuntimeError(
+                f"{name} is set, but it was removed together with the kernel "
+                "it selected; unset it")
+
+
+_switches_checked = False
+
+
 def ext():
+    # once per process here (ext() sits on the per-job host path, which the
+    # sequential benchmark sees); require_gpu_ext() checks every time
+    global _switches_checked
+    if not _switches_checked:
+        check_retired_switches()
+        _switches_checked = True
     if _ext is None:
         raise ImportError(
             "mapreduce_amd._hip_ops is not built; run "
@@ -38,6 +64,7 @@ def ext():
 def require_gpu_ext() -> None:
     """Loud failure when a GPU is present but the HIP extension is not —
     GPU runs must never silently use an eager fallback."""
+    check_retired_switches()
     if torch.cuda.is_available():
         ext()
 

@@ -15,10 +15,12 @@
 //          with 32-bit selects + v_alignbyte.  tokenize_v6_kernel differs
 //          only in that it stages the tile in the open (barrier, load,
 //          wait, LDS write, barrier) and extracts every chunk with 64-bit
-//          selects and a funnel shift (MR_TOKENIZE_V6=1, and the sweep /
-//          ablation / bucketed-spill instantiations); tokenize_kernel /
-//          tokenize_count_kernel / tokenize_spill / v5 are earlier
-//          structures kept for tests and recorded A/Bs
+//          selects and a funnel shift; it is kept as v7's A/B partner
+//          (MR_TOKENIZE_V6=1) with the same five instantiations.
+//          tokenize_kernel (plain (hash, pos) emit, has a CPU twin, used
+//          by the inverted index's small paths) and tokenize_count_kernel
+//          (fused tokenize + table count, the low-memory mode) are the
+//          two other tokenizers
 //   K5     bucket_count_kernel    — per-bucket LDS count of the
 //          top-byte-partitioned spill tail; hash_insert/extract are the
 //          generic table ops (extract has a chunked-compaction v2 for
@@ -228,439 +230,17 @@ __global__ __launch_bounds__(256) void tokenize_count_kernel(
 }
 
 // ---------------------------------------------------------------------------
-// K2 streaming form: tokenize -> compact (hash, pos) spill arrays.
-// One global offset reservation per THREAD per tile (not per word), writes
-// mostly contiguous.  Feeds the bucketize + LDS-count pipeline below — the
-// streaming replacement for per-word random table probes (which measured
-// latency-bound at ~600 cycles/word).
-// ---------------------------------------------------------------------------
-
-__global__ __launch_bounds__(256) void tokenize_spill_kernel(
-    const u8* __restrict__ text, long n, u64 pos_base,
-    u64* __restrict__ out_hash, u64* __restrict__ out_pos,
-    unsigned long long* __restrict__ counter, long cap) {
-  __shared__ u8 tile[TOK_TILE + TOK_HALO];
-  long tile0 = (long)blockIdx.x * TOK_TILE;
-  long tstride = (long)gridDim.x * TOK_TILE;
-  for (long base = tile0; base < n; base += tstride) {
-    __syncthreads();
-    long avail = n - base;
-    long want = avail < TOK_TILE + TOK_HALO ? avail : TOK_TILE + TOK_HALO;
-    for (int o = threadIdx.x * 16; o < want; o += blockDim.x * 16) {
-      if (o + 16 <= want && (((uintptr_t)&text[base + o]) & 15) == 0) {
-        *(uint4*)&tile[o] = *(const uint4*)&text[base + o];
-      } else {
-        for (int b = 0; b < 16 && o + b < want; ++b)
-          tile[o + b] = text[base + o + b];
-      }
-    }
-    __syncthreads();
-    long my0 = (long)threadIdx.x * TOK_BYTES;
-    long myend = my0 + TOK_BYTES;
-    if (myend > avail) myend = avail;
-    if (my0 >= myend) continue;
-    // first pass: find words in my window (register-buffered, <= 8/window)
-    u64 wh[8];
-    u64 wp[8];
-    int nw = 0;
-    u8 prev = (base + my0 == 0) ? ' ' : (my0 ? tile[my0 - 1] : text[base - 1]);
-    for (long i = my0; i < myend; ++i) {
-      u8 c = tile[i];
-      if (!is_ws(c) && is_ws(prev)) {
-        u64 h = FNV64_OFFSET;
-        long j = i;
-        while (j < want) {
-          u8 cc = tile[j];
-          if (is_ws(cc)) break;
-          h ^= cc;
-          h *= FNV64_PRIME;
-          ++j;
-        }
-        if (j == want && base + j < n) {
-          long g = base + j;
-          while (g < n) {
-            u8 cc = text[g];
-            if (is_ws(cc)) break;
-            h ^= cc;
-            h *= FNV64_PRIME;
-            ++g;
-          }
-          j = g - base;
-        }
-        long len = j - i;
-        if (len > 0xFFFF) len = 0xFFFF;
-        wh[nw] = remap_key(h);  // keep HT_EMPTY free for table sentinels
-        wp[nw] = ((pos_base + (u64)(base + i)) << 16) | (u64)len;
-        ++nw;
-      }
-      prev = c;
-    }
-    // one reservation per thread (wave-coalesced by the compiler where
-    // possible), then contiguous writes
-    if (nw) {
-      unsigned long long o = atomicAdd(counter, (unsigned long long)nw);
-      for (int w = 0; w < nw; ++w) {
-        if ((long)o + w < cap) {
-          out_hash[o + w] = wh[w];
-          out_pos[o + w] = wp[w];
-        }
-      }
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// K2+K5 v4: tokenize with per-block LDS cache; cache MISSES spill to the
-// compact (hash,pos) stream instead of probing the global table.  The Zipf
-// head aggregates in LDS (one ht_add per block per hot word at flush); the
-// tail streams out for the bucketize+LDS-count pipeline.  No per-word
-// global-memory probe anywhere.
-// ---------------------------------------------------------------------------
-
-__global__ __launch_bounds__(256) void tokenize_cache_spill_kernel(
-    const u8* __restrict__ text, long n, u64 pos_base,
-    u64* __restrict__ tkeys, i64* __restrict__ tvals, u64* __restrict__ texm,
-    u64 cap_mask, u64* __restrict__ out_hash, u64* __restrict__ out_pos,
-    unsigned long long* __restrict__ spill_counter, long spill_cap,
-    unsigned long long* __restrict__ nwords) {
-  __shared__ u8 tile[TOK_TILE + TOK_HALO];
-  __shared__ u64 ckeys[TOK_CACHE];
-  __shared__ u64 cpos[TOK_CACHE];
-  __shared__ u32 ccnt[TOK_CACHE];
-  for (int s = threadIdx.x; s < TOK_CACHE; s += blockDim.x) {
-    ckeys[s] = HT_EMPTY;
-    ccnt[s] = 0;
-  }
-  unsigned long long my_words = 0;
-  long tile0 = (long)blockIdx.x * TOK_TILE;
-  long tstride = (long)gridDim.x * TOK_TILE;
-  for (long base = tile0; base < n; base += tstride) {
-    __syncthreads();
-    long avail = n - base;
-    long want = avail < TOK_TILE + TOK_HALO ? avail : TOK_TILE + TOK_HALO;
-    for (int o = threadIdx.x * 16; o < want; o += blockDim.x * 16) {
-      if (o + 16 <= want && (((uintptr_t)&text[base + o]) & 15) == 0) {
-        *(uint4*)&tile[o] = *(const uint4*)&text[base + o];
-      } else {
-        for (int b = 0; b < 16 && o + b < want; ++b)
-          tile[o + b] = text[base + o + b];
-      }
-    }
-    __syncthreads();
-    long my0 = (long)threadIdx.x * TOK_BYTES;
-    long myend = my0 + TOK_BYTES;
-    if (myend > avail) myend = avail;
-    if (my0 >= myend) continue;
-    u64 sh[8];  // this window's cache misses
-    u64 sp[8];
-    int ns = 0;
-    u8 prev = (base + my0 == 0) ? ' ' : (my0 ? tile[my0 - 1] : text[base - 1]);
-    for (long i = my0; i < myend; ++i) {
-      u8 c = tile[i];
-      if (!is_ws(c) && is_ws(prev)) {
-        u64 h = FNV64_OFFSET;
-        long j = i;
-        while (j < want) {
-          u8 cc = tile[j];
-          if (is_ws(cc)) break;
-          h ^= cc;
-          h *= FNV64_PRIME;
-          ++j;
-        }
-        if (j == want && base + j < n) {
-          long g = base + j;
-          while (g < n) {
-            u8 cc = text[g];
-            if (is_ws(cc)) break;
-            h ^= cc;
-            h *= FNV64_PRIME;
-            ++g;
-          }
-          j = g - base;
-        }
-        long len = j - i;
-        if (len > 0xFFFF) len = 0xFFFF;
-        u64 k = remap_key(h);
-        u64 p = ((pos_base + (u64)(base + i)) << 16) | (u64)len;
-        ++my_words;
-        u32 slot = (u32)((k ^ (k >> 32)) & (TOK_CACHE - 1));
-        bool done = false;
-        for (int pr = 0; pr < TOK_PROBE; ++pr) {
-          u64 cur = ckeys[slot];
-          if (cur == k) {
-            atomicAdd(&ccnt[slot], 1u);
-            done = true;
-            break;
-          }
-          if (cur == HT_EMPTY) {
-            u64 prevk = atomicCAS((unsigned long long*)&ckeys[slot],
-                                  (unsigned long long)HT_EMPTY,
-                                  (unsigned long long)k);
-            if (prevk == HT_EMPTY) cpos[slot] = p;
-            if (prevk == HT_EMPTY || prevk == k) {
-              atomicAdd(&ccnt[slot], 1u);
-              done = true;
-              break;
-            }
-          }
-          slot = (slot + 1) & (TOK_CACHE - 1);
-        }
-        if (!done) {
-          sh[ns] = k;
-          sp[ns] = p;
-          ++ns;
-        }
-      }
-      prev = c;
-    }
-    if (ns) {
-      unsigned long long o = atomicAdd(spill_counter, (unsigned long long)ns);
-      for (int w = 0; w < ns; ++w)
-        if ((long)o + w < spill_cap) {
-          out_hash[o + w] = sh[w];
-          out_pos[o + w] = sp[w];
-        }
-    }
-  }
-  __syncthreads();
-  for (int s = threadIdx.x; s < TOK_CACHE; s += blockDim.x)
-    if (ckeys[s] != HT_EMPTY && ccnt[s])
-      ht_add(ckeys[s], cpos[s], (i64)ccnt[s], tkeys, tvals, texm, cap_mask);
-  unsigned long long ws = my_words;
-  for (int off = 32; off > 0; off >>= 1) ws += __shfl_down(ws, off, WAVE);
-  if (lane_id() == 0 && ws) atomicAdd(nwords, ws);
-}
-
-// ---------------------------------------------------------------------------
-// K2+K5 v5: mask-based tokenizer with per-tile word list.
-// The v4 structure paid the cache-insert cost at nearly every byte position
-// (insert code inside the divergent per-byte loop).  v5 decouples:
-//   A. branchless classification — each thread turns its 16 LDS bytes into
-//      a whitespace bitmask (compile-time unrolled extracts, no branches);
-//   B. word enumeration from mask pairs (starts = ~m & (m<<1); length =
-//      ctz of the shifted mask) into a per-tile LDS word list, slots
-//      reserved with one wave-prefix + one LDS atomic per wave;
-//   C. balanced processing — lanes take words round-robin from the list
-//      (every lane active), hash via aligned u64 funnel reads from LDS,
-//      insert into the direct-probed LDS cache, wave-aggregated spill of
-//      misses (one global atomic per wave per round).
-// ---------------------------------------------------------------------------
-
-#define TOKV5_MARK 0xFFFu  // len field marker: word longer than the mask
-                           // window — rescan from global text
-
-__global__ __launch_bounds__(256) void tokenize_v5_kernel(
-    const u8* __restrict__ text, long n, u64 pos_base,
-    u64* __restrict__ tkeys, i64* __restrict__ tvals, u64* __restrict__ texm,
-    u64 cap_mask, u64* __restrict__ out_hash, u64* __restrict__ out_pos,
-    unsigned long long* __restrict__ spill_counter, long spill_cap,
-    unsigned long long* __restrict__ nwords) {
-  __shared__ __align__(16) u8 tile[TOK_TILE + TOK_HALO];
-  __shared__ unsigned short wsmask[260];  // 256 windows + 4 halo windows
-  __shared__ u32 wlist[TOK_TILE / 2 + 64];
-  __shared__ u32 wl_count;
-  __shared__ u64 ckeys[TOK_CACHE];
-  __shared__ u64 cpos[TOK_CACHE];
-  __shared__ u32 ccnt[TOK_CACHE];
-  for (int s = threadIdx.x; s < TOK_CACHE; s += blockDim.x) {
-    ckeys[s] = HT_EMPTY;
-    ccnt[s] = 0;
-  }
-  const int tid = threadIdx.x;
-  const int lane = tid & (WAVE - 1);
-  const u64 lt_mask = ((u64)1 << lane) - 1;
-  unsigned long long my_words = 0;
-  long tile0 = (long)blockIdx.x * TOK_TILE;
-  long tstride = (long)gridDim.x * TOK_TILE;
-  for (long base = tile0; base < n; base += tstride) {
-    __syncthreads();  // previous tile fully consumed
-    long avail = n - base;
-    long want = avail < TOK_TILE + TOK_HALO ? avail : TOK_TILE + TOK_HALO;
-    for (int o = tid * 16; o < want; o += blockDim.x * 16) {
-      if (o + 16 <= want && (((uintptr_t)&text[base + o]) & 15) == 0) {
-        *(uint4*)&tile[o] = *(const uint4*)&text[base + o];
-      } else {
-        for (int b = 0; b < 16 && o + b < want; ++b)
-          tile[o + b] = text[base + o + b];
-      }
-    }
-    if (tid == 0) wl_count = 0;
-    __syncthreads();
-    // ---- A: classify 16 bytes -> ws bitmask (bit set = whitespace)
-    {
-      int w0 = tid * 16;
-      u32 m = 0xFFFFu;
-      if (w0 < want) {
-        const uint4 v = *(const uint4*)&tile[w0];
-        m = 0;
-        const u32 rs[4] = {v.x, v.y, v.z, v.w};
-        #pragma unroll
-        for (int r = 0; r < 4; ++r)
-          #pragma unroll
-          for (int b = 0; b < 4; ++b) {
-            u8 c = (u8)(rs[r] >> (8 * b));
-            m |= (u32)is_ws(c) << (r * 4 + b);
-          }
-        long lim = want - w0;
-        if (lim < 16) m |= ~((1u << lim) - 1) & 0xFFFFu;
-      }
-      wsmask[tid] = (unsigned short)m;
-      if (tid < 4) {  // halo windows
-        int h0 = TOK_TILE + tid * 16;
-        u32 hm = 0xFFFFu;
-        if (h0 < want) {
-          hm = 0;
-          #pragma unroll
-          for (int b = 0; b < 16; ++b) {
-            u32 wsb = (h0 + b < want) ? (u32)is_ws(tile[h0 + b]) : 1u;
-            hm |= wsb << b;
-          }
-        }
-        wsmask[256 + tid] = (unsigned short)hm;
-      }
-    }
-    __syncthreads();
-    // ---- B: word starts in my window -> LDS word list
-    {
-      int w0 = tid * 16;
-      u32 m = wsmask[tid];
-      u32 nx = (tid < 255) ? wsmask[tid + 1] : wsmask[256];
-      u32 m32 = m | (nx << 16);
-      u32 prevb;
-      if (tid > 0)
-        prevb = (wsmask[tid - 1] >> 15) & 1u;
-      else
-        prevb = (base == 0) ? 1u : (u32)is_ws(text[base - 1]);
-      u32 sm = ~m32 & ((m32 << 1) | prevb) & 0xFFFFu;
-      // starts must lie inside the data (not the padded region)
-      long lim = avail - w0;
-      if (lim <= 0) sm = 0;
-      else if (lim < 16) sm &= (1u << lim) - 1;
-      int nw = __popc(sm);
-      my_words += nw;
-      // wave-exclusive prefix of nw, one LDS atomic per wave
-      u32 incl = (u32)nw;
-      #pragma unroll
-      for (int off = 1; off < WAVE; off <<= 1) {
-        u32 x = __shfl_up(incl, off, WAVE);
-        if (lane >= off) incl += x;
-      }
-      u32 wave_total = __shfl(incl, WAVE - 1, WAVE);
-      u32 wave_base = 0;
-      if (lane == 0 && wave_total)
-        wave_base = atomicAdd(&wl_count, wave_total);
-      wave_base = __shfl(wave_base, 0, WAVE);
-      u32 slot = wave_base + incl - (u32)nw;
-      while (sm) {
-        int s = __ffs(sm) - 1;
-        sm &= sm - 1;
-        u32 t = m32 >> s;
-        u32 len = t ? (u32)(__ffs(t) - 1) : TOKV5_MARK;
-        if (len == 0) len = TOKV5_MARK;  // cannot happen (bit s clear)
-        wlist[slot++] = (u32)(w0 + s) | (len << 13);
-      }
-    }
-    __syncthreads();
-    // ---- C: balanced hash + count/spill
-    int tot = (int)wl_count;
-    const u64* t64 = (const u64*)tile;
-    for (int widx = tid; widx < tot + (WAVE - 1); widx += blockDim.x) {
-      // padded loop bound keeps whole waves together for ballots; inactive
-      // lanes carry valid=false
-      bool valid = widx < tot;
-      u64 h = FNV64_OFFSET;
-      u64 p = 0;
-      u64 k = 0;
-      if (valid) {
-        u32 pk = wlist[widx];
-        int s = (int)(pk & 0x1FFFu);
-        u32 len = pk >> 13;
-        if (len != TOKV5_MARK) {
-          int q = s >> 3;
-          int sh = (s & 7) * 8;
-          u64 cur = t64[q] >> sh;
-          int have = 8 - (s & 7);
-          for (u32 b = 0; b < len; ++b) {
-            if (have == 0) {
-              cur = t64[++q];
-              have = 8;
-            }
-            h = (h ^ (cur & 0xFF)) * FNV64_PRIME;
-            cur >>= 8;
-            --have;
-          }
-        } else {  // long word: rescan from global
-          long g = base + s;
-          while (g < n && !is_ws(text[g])) {
-            h = (h ^ text[g]) * FNV64_PRIME;
-            ++g;
-          }
-          len = (u32)((g - (base + s)) > 0xFFFF ? 0xFFFF : g - (base + s));
-        }
-        k = remap_key(h);
-        p = ((pos_base + (u64)(base + s)) << 16) | (u64)(len & 0xFFFF);
-      }
-      // cache insert (probe <= TOK_PROBE)
-      bool miss = valid;
-      if (valid) {
-        u32 slot = (u32)((k ^ (k >> 32)) & (TOK_CACHE - 1));
-        for (int pr = 0; pr < TOK_PROBE; ++pr) {
-          u64 cur = ckeys[slot];
-          if (cur == k) {
-            atomicAdd(&ccnt[slot], 1u);
-            miss = false;
-            break;
-          }
-          if (cur == HT_EMPTY) {
-            u64 prevk = atomicCAS((unsigned long long*)&ckeys[slot],
-                                  (unsigned long long)HT_EMPTY,
-                                  (unsigned long long)k);
-            if (prevk == HT_EMPTY) cpos[slot] = p;
-            if (prevk == HT_EMPTY || prevk == k) {
-              atomicAdd(&ccnt[slot], 1u);
-              miss = false;
-              break;
-            }
-          }
-          slot = (slot + 1) & (TOK_CACHE - 1);
-        }
-      }
-      // wave-aggregated spill (one global atomic per wave per round)
-      u64 miss_mask = __ballot(miss);
-      if (miss_mask) {
-        int leader = __ffsll((unsigned long long)miss_mask) - 1;
-        unsigned long long o = 0;
-        if (lane == leader)
-          o = atomicAdd(spill_counter,
-                        (unsigned long long)__popcll(miss_mask));
-        o = __shfl(o, leader, WAVE);
-        if (miss) {
-          long mi = (long)o + __popcll(miss_mask & lt_mask);
-          if (mi < spill_cap) {
-            out_hash[mi] = k;
-            out_pos[mi] = p;
-          }
-        }
-      }
-    }
-  }
-  __syncthreads();
-  for (int s = tid; s < TOK_CACHE; s += blockDim.x)
-    if (ckeys[s] != HT_EMPTY && ccnt[s])
-      ht_add(ckeys[s], cpos[s], (i64)ccnt[s], tkeys, tvals, texm, cap_mask);
-  unsigned long long ws = my_words;
-  for (int off = 32; off > 0; off >>= 1) ws += __shfl_down(ws, off, WAVE);
-  if (lane == 0 && ws) atomicAdd(nwords, ws);
-}
-
-// ---------------------------------------------------------------------------
-// K2+K5 v6: v4's single-phase structure + v5's branchless scan.
+// K2+K5 v6: single-phase window tokenizer, the A/B partner of v7 below
+// (MR_TOKENIZE_V6=1).  A block stages a 4 KB tile (+64 B halo) into LDS.
 // Per thread: classify its 16 LDS bytes (+16 lookahead) into a whitespace
-// bitmask with compile-time-unrolled extracts, iterate word starts with
-// ffs (~words, not ~bytes, iterations), hash from REGISTERS via funnel
-// shifts (zero LDS re-reads), insert into the v4 LDS cache, spill misses.
-// Same two barriers per tile as v4 — the v5 word-list experiment showed
-// extra barriers/LDS cost more than lane balance buys.
+// bitmask (SWAR, branchless), iterate word starts with ffs (~words, not
+// ~bytes, iterations), hash from REGISTERS via funnel shifts (zero LDS
+// re-reads), count the word in the block's LDS cache, spill the misses
+// through the wave-chunked allocator.  Two barriers per tile — a word-list
+// restructure with a third measured 2x slower: extra barriers and LDS cost
+// more than lane balance buys (NOTES.md, recorded negative results).
+// Template flags add spill-all (no cache) and the fused (word, doc)
+// composite keys of the inverted index.
 // ---------------------------------------------------------------------------
 
 // (pos << 16 | len) of the word at the lowest set bit of `smw` (the
@@ -675,28 +255,21 @@ __device__ __forceinline__ u64 v6_spill_pos(u64 wpos0, u32 smw, u32 m32,
   return ((wpos0 + (u64)s) << 16) | (u64)len;
 }
 
-// MODE (ablation, §5.4 rule 8): 0=full, 1=stage+classify, 2=+hash, 3=+cache (no spill)
-template <int CACHE_N, bool GPOS, int TILE_N, int MODE = 0,
+// threads per block of every v6 / v7 launch: one window pass of
+// TOK_THREADS x 16 bytes is the tile.  The launchers static_assert their
+// block size against it.
+constexpr int TOK_THREADS = 256;
+
+template <int CACHE_N, bool GPOS,
           bool SPILL_ALL = false,  // emit every word (no cache)
           bool COMPOSITE = false,  // keys = wordhash ^ splitmix64(doc)
                                    // (doc from split_off binary search) —
                                    // the inverted-index path, fusing the
                                    // doc lookup + mix into the tokenizer
-          int SCHUNK = 512,  // chunked-allocator reservation size: pads
+          int SCHUNK = 512>  // chunked-allocator reservation size: pads
                              // scale with it (waves x SCHUNK/2 wasted
                              // tail entries) vs atomic amortization
-          int NBKT = 0,  // >0: bucketed direct spill — misses go straight
-                         // into per-top-byte-bucket regions (out[b*cap ..])
-                         // via wave-cooperative reservation on NBKT
-                         // counters, replacing the single-array spill +
-                         // the later radix_pass(56) bucketize entirely
-                         // (that pass measured ~320 us/step: hist 63 +
-                         // scatter 255, profiles/kernel_stats_final_step)
-          int BLOCKN = 256>  // threads/block; one window pass covers
-                             // BLOCKN*16 bytes, so TILE_N scales with it
-                             // (512/8192 trades +2 KB tile LDS for 2x
-                             // waves per block — occupancy probe)
-__global__ __launch_bounds__(BLOCKN) void tokenize_v6_kernel(
+__global__ __launch_bounds__(TOK_THREADS) void tokenize_v6_kernel(
     const u8* __restrict__ text, long n, u64 pos_base,
     u64* __restrict__ tkeys, i64* __restrict__ tvals, u64* __restrict__ texm,
     u64 cap_mask, u64* __restrict__ out_hash, u64* __restrict__ out_pos,
@@ -704,6 +277,7 @@ __global__ __launch_bounds__(BLOCKN) void tokenize_v6_kernel(
     unsigned long long* __restrict__ nwords, u64* __restrict__ cpos_g,
     const i64* __restrict__ split_off = nullptr, int nsplit_off = 0,
     long doc_base = 0) {
+  constexpr int TILE_N = TOK_THREADS * TOK_BYTES;  // one window pass per tile
   __shared__ __align__(16) u8 tile[TILE_N + TOK_HALO];
   __shared__ u64 ckeys[CACHE_N];
   // exemplar positions: LDS normally; with GPOS a global side-buffer
@@ -742,8 +316,12 @@ __global__ __launch_bounds__(BLOCKN) void tokenize_v6_kernel(
       }
     }
     __syncthreads();
-    for (int wnd = 0; wnd < TILE_N / (BLOCKN * TOK_BYTES); ++wnd) {
-    long my0 = ((long)tid + (long)wnd * BLOCKN) * TOK_BYTES;
+    // One window pass covers the tile.  It is still written as a loop (of
+    // one pass, body not indented): without the loop the compiler schedules
+    // this kernel differently, 3 to 5 instructions longer, and v6 is kept
+    // as it was measured.
+    for (int wnd = 0; wnd < 1; ++wnd) {
+    long my0 = (long)tid * TOK_BYTES;
     // whole wave stays in the loop (the spill wave-scan below needs every
     // lane present); out-of-range lanes just contribute ns = 0
     bool wactive = my0 < avail;
@@ -770,7 +348,6 @@ __global__ __launch_bounds__(BLOCKN) void tokenize_v6_kernel(
     long limw = avail - my0;  // starts must be real data bytes
     if (limw < 16) sm &= (limw <= 0) ? 0u : ((1u << limw) - 1);
     my_words += __popc(sm);
-    if (MODE == 1) { my_words += m32; sm = 0; }
     // fully-unrolled word loop (a 16-byte window holds <= 8 words):
     // compile-time slot indices keep the miss buffers in REGISTERS —
     // runtime-indexed arrays here lower to divergent v_movrel waterfalls
@@ -833,7 +410,6 @@ __global__ __launch_bounds__(BLOCKN) void tokenize_v6_kernel(
         len = (u32)(wlen > 0xFFFF ? 0xFFFF : wlen);
         long_len = len;
       }
-      if (MODE == 2) { my_words += h; continue; }
       if (COMPOSITE) {
         // fuse the (word, doc) composite: doc from the split-offset
         // table (L2-resident; ~10-step binary search per word)
@@ -872,105 +448,54 @@ __global__ __launch_bounds__(BLOCKN) void tokenize_v6_kernel(
         slot = (slot + 1) & (CACHE_N - 1);
       }
       if (!done) {
-        if (MODE == 3) {
-          my_words += 1;
-        } else {
-          miss_mask |= 1u << wi;  // wi is compile-time: register slot
-          sh_[wi] = k;
-        }
+        miss_mask |= 1u << wi;  // wi is compile-time: register slot
+        sh_[wi] = k;
       }
     }
     // window-level spill reservation: every lane of the wave is present
     // here (wactive design above)
-    if (NBKT > 0) {
-      // bucketed direct spill: for each word slot round, group the wave's
-      // misses by top-byte bucket and reserve per-bucket slots with ONE
-      // atomic per distinct bucket per round.  The NBKT distinct counter
-      // addresses spread the atomic traffic (the same-address serialization
-      // that motivated the chunked allocator does not apply), writes of a
-      // round's same-bucket members are adjacent, and no pad entries exist
-      // — counters are exact per-bucket lengths.
-      u32 smw = sm0;
-      #pragma unroll
-      for (int wi = 0; wi < 8; ++wi) {
-        unsigned long long pending =
-            __ballot((miss_mask >> wi) & 1u);
-        if (__ballot(miss_mask >> wi) == 0) break;  // no lane has more slots
-        bool mine = (miss_mask >> wi) & 1u;
-        u64 mypos = mine ? v6_spill_pos(wpos0, smw, m32, long_len) : 0;
-        smw &= smw - 1;
-        u64 bk = mine ? (sh_[wi] >> 56) % (u64)NBKT : 0;
-        int lane = threadIdx.x & (WAVE - 1);
-        unsigned long long lt_mask =
-            (lane == 63) ? ~0ull >> 1 : ((1ull << lane) - 1);
-        while (pending) {
-          int leader = __ffsll(pending) - 1;
-          u64 lead_bk = __shfl(bk, leader, WAVE);
-          unsigned long long members =
-              __ballot(mine && bk == lead_bk) & pending;
-          int nmem = __popcll(members);
-          unsigned long long base = 0;
-          if (lane == leader)
-            base = atomicAdd(&spill_counter[lead_bk],
-                             (unsigned long long)nmem);
-          base = __shfl(base, leader, WAVE);
-          if (members & (1ull << lane)) {
-            long r = (long)base + __popcll(members & lt_mask);
-            if (r < spill_cap) {  // overflow: counter runs past cap — the
-              long o = (long)lead_bk * spill_cap + r;  // host detects
-              out_hash[o] = sh_[wi];                   // max(cnt) > cap
-              out_pos[o] = mypos;
-            }
-          }
-          pending &= ~members;
+    u32 my_ns = (u32)__popc(miss_mask);
+    // (four ballots + mbcnt instead of these six dependent shuffles
+    // measured no gain: profiles/tokenizer_occupancy_r04.md)
+    u32 incl = my_ns;
+    #pragma unroll
+    for (int off = 1; off < WAVE; off <<= 1) {
+      u32 x = __shfl_up(incl, off, WAVE);
+      if ((threadIdx.x & (WAVE - 1)) >= off) incl += x;
+    }
+    u32 wave_total = __shfl(incl, WAVE - 1, WAVE);
+    int lane = threadIdx.x & (WAVE - 1);
+    if (wave_total && (int)wave_total > wleft) {
+      // retire the old chunk's tail (pad with HT_EMPTY) + grab a new
+      // one (at least a window's worth: a pathological window can
+      // produce up to 64x8 misses, more than a small SPILL_CHUNK)
+      for (int i = lane; i < wleft; i += WAVE)
+        if (wchunk + i < spill_cap) out_hash[wchunk + i] = HT_EMPTY;
+      int grab = (int)wave_total > SPILL_CHUNK ? (int)wave_total
+                                               : SPILL_CHUNK;
+      unsigned long long nb = 0;
+      if (lane == 0)
+        nb = atomicAdd(spill_counter, (unsigned long long)grab);
+      wchunk = (long)__shfl(nb, 0, WAVE);
+      wleft = grab;
+    }
+    long o = wchunk + (long)(incl - my_ns);
+    if (wave_total) {
+      wchunk += wave_total;
+      wleft -= (int)wave_total;
+    }
+    u32 smw = sm0;
+    #pragma unroll
+    for (int wi = 0; wi < 8; ++wi) {
+      if (miss_mask & (1u << wi)) {
+        u64 p = v6_spill_pos(wpos0, smw, m32, long_len);
+        if (o < spill_cap) {
+          out_hash[o] = sh_[wi];
+          out_pos[o] = p;
         }
+        ++o;
       }
-    } else {
-      u32 my_ns = (u32)__popc(miss_mask);
-      // (four ballots + mbcnt instead of these six dependent shuffles
-      // measured no gain: profiles/tokenizer_occupancy_r04.md)
-      u32 incl = my_ns;
-      #pragma unroll
-      for (int off = 1; off < WAVE; off <<= 1) {
-        u32 x = __shfl_up(incl, off, WAVE);
-        if ((threadIdx.x & (WAVE - 1)) >= off) incl += x;
-      }
-      u32 wave_total = __shfl(incl, WAVE - 1, WAVE);
-      int lane = threadIdx.x & (WAVE - 1);
-      if (wave_total && (int)wave_total > wleft) {
-        // retire the old chunk's tail (pad with HT_EMPTY) + grab a new
-        // one (at least a window's worth: a pathological window can
-        // produce up to 64x8 misses, more than a small SPILL_CHUNK)
-        for (int i = lane; i < wleft; i += WAVE)
-          if (wchunk + i < spill_cap) out_hash[wchunk + i] = HT_EMPTY;
-        int grab = (int)wave_total > SPILL_CHUNK ? (int)wave_total
-                                                 : SPILL_CHUNK;
-        unsigned long long nb = 0;
-        if (lane == 0)
-          nb = atomicAdd(spill_counter, (unsigned long long)grab);
-        wchunk = (long)__shfl(nb, 0, WAVE);
-        wleft = grab;
-      }
-      long o = wchunk + (long)(incl - my_ns);
-      if (wave_total) {
-        wchunk += wave_total;
-        wleft -= (int)wave_total;
-      }
-      u32 smw = sm0;
-      #pragma unroll
-      for (int wi = 0; wi < 8; ++wi) {
-        if (miss_mask & (1u << wi)) {
-          u64 p = v6_spill_pos(wpos0, smw, m32, long_len);
-          if (MODE == 4) {
-            my_words += sh_[wi] + p + (u64)o;
-          } else if (o < spill_cap) {
-            out_hash[o] = sh_[wi];
-            out_pos[o] = p;
-          }
-          ++o;
-        }
-        smw &= smw - 1;
-      }
+      smw &= smw - 1;
     }
     }  // wnd
   }
@@ -1012,19 +537,23 @@ __global__ __launch_bounds__(BLOCKN) void tokenize_v6_kernel(
 //     v_alignbyte, instead of 64-bit selects over q0..q3 and a 64-bit funnel
 //     shift: 10 % fewer VALU instructions per job.  Later chunks of longer
 //     words keep v6's form.
+//
+// The window code below is a copy of v6's on purpose.  Moving it into shared
+// __forceinline__ helpers was tried piece by piece (masks, later-chunk hash,
+// long-word scan, cache probe, spill phase, final flush): every piece changed
+// the generated code of v6, and all but the mask construction that of v7
+// (from one commuted operand to 200 instructions), and wait placement in
+// this loop is fragile.  So a change to the window is made in both kernels;
+// the v6 == v7 bit-identity test keeps them in step.
 // ---------------------------------------------------------------------------
 #define V7_WAIT_VM0 0x0F70  // s_waitcnt vmcnt(0) alone (gfx9 encoding)
-// threads per block of every v7 launch: one window pass of V7_BLOCK x 16
-// bytes is the tile, and the staging loops stride by it.  The launchers
-// static_assert their block size against it.
-constexpr int V7_BLOCK = 256;
 
 template <int TILE_N>
 __device__ __forceinline__ void v7_stage_plain(u8* tile,
                                                const u8* __restrict__ text,
                                                long base, long want,
                                                bool aligned) {
-  for (int o = threadIdx.x * 16; o < want; o += V7_BLOCK * 16) {
+  for (int o = threadIdx.x * 16; o < want; o += TOK_THREADS * 16) {
     if (aligned && o + 16 <= want) {
       *(uint4*)&tile[o] = *(const uint4*)&text[base + o];
     } else {
@@ -1037,7 +566,7 @@ __device__ __forceinline__ void v7_stage_plain(u8* tile,
 template <int CACHE_N, bool GPOS, bool SPILL_ALL = false,
           bool COMPOSITE = false, int SCHUNK = 512>
 // 5 waves per SIMD asked for where the LDS admits 5 blocks: 96 VGPRs, as v6
-__global__ __launch_bounds__(V7_BLOCK, GPOS || SPILL_ALL ? 5 : 3)
+__global__ __launch_bounds__(TOK_THREADS, GPOS || SPILL_ALL ? 5 : 3)
 void tokenize_v7_kernel(
     const u8* __restrict__ text, long n, u64 pos_base,
     u64* __restrict__ tkeys, i64* __restrict__ tvals, u64* __restrict__ texm,
@@ -1046,7 +575,7 @@ void tokenize_v7_kernel(
     unsigned long long* __restrict__ nwords, u64* __restrict__ cpos_g,
     const i64* __restrict__ split_off = nullptr, int nsplit_off = 0,
     long doc_base = 0) {
-  constexpr int TILE_N = V7_BLOCK * TOK_BYTES;  // one window pass per tile
+  constexpr int TILE_N = TOK_THREADS * TOK_BYTES;  // one window pass per tile
   __shared__ __align__(16) u8 tile[TILE_N + TOK_HALO];
   __shared__ u64 ckeys[CACHE_N];
   __shared__ u64 cpos_l[GPOS ? 1 : CACHE_N];
@@ -1301,132 +830,6 @@ void tokenize_v7_kernel(
   if (lane == 0 && ws) atomicAdd(nwords, ws);
 }
 
-// Ablation copy of the tokenize kernel (diagnosis only — §5.4 rule 8:
-// ablate empirically before optimizing).  mode: 1=stage tiles only,
-// 2=+word-boundary scan (count only), 3=+FNV hash, 4=+LDS cache insert,
-// 5=full (with spill).  Results accumulate into sink to stay live.
-__global__ __launch_bounds__(256) void tok_ablate_kernel(
-    const u8* __restrict__ text, long n, int mode,
-    u64* __restrict__ ckeys_g /*scratch cap>=2^20*/, i64* __restrict__ sink,
-    u64* __restrict__ out_hash, u64* __restrict__ out_pos,
-    unsigned long long* __restrict__ spill_counter, long spill_cap) {
-  __shared__ u8 tile[TOK_TILE + TOK_HALO];
-  __shared__ u64 ckeys[TOK_CACHE];
-  __shared__ u64 cpos[TOK_CACHE];
-  __shared__ u32 ccnt[TOK_CACHE];
-  for (int s = threadIdx.x; s < TOK_CACHE; s += blockDim.x) {
-    ckeys[s] = HT_EMPTY;
-    ccnt[s] = 0;
-  }
-  unsigned long long acc = 0;
-  long tile0 = (long)blockIdx.x * TOK_TILE;
-  long tstride = (long)gridDim.x * TOK_TILE;
-  for (long base = tile0; base < n; base += tstride) {
-    __syncthreads();
-    long avail = n - base;
-    long want = avail < TOK_TILE + TOK_HALO ? avail : TOK_TILE + TOK_HALO;
-    for (int o = threadIdx.x * 16; o < want; o += blockDim.x * 16) {
-      if (o + 16 <= want && (((uintptr_t)&text[base + o]) & 15) == 0) {
-        *(uint4*)&tile[o] = *(const uint4*)&text[base + o];
-      } else {
-        for (int b = 0; b < 16 && o + b < want; ++b)
-          tile[o + b] = text[base + o + b];
-      }
-    }
-    __syncthreads();
-    if (mode == 1) {  // consume a few tile bytes so staging stays live
-      acc += tile[threadIdx.x];
-      continue;
-    }
-    long my0 = (long)threadIdx.x * TOK_BYTES;
-    long myend = my0 + TOK_BYTES;
-    if (myend > avail) myend = avail;
-    if (my0 >= myend) continue;
-    u64 sh[8];
-    u64 sp[8];
-    int ns = 0;
-    u8 prev = (base + my0 == 0) ? ' ' : (my0 ? tile[my0 - 1] : text[base - 1]);
-    for (long i = my0; i < myend; ++i) {
-      u8 c = tile[i];
-      if (!is_ws(c) && is_ws(prev)) {
-        u64 h = FNV64_OFFSET;
-        long j = i;
-        if (mode == 2) {  // boundary-scan only: find end without hashing
-          while (j < want && !is_ws(tile[j])) ++j;
-          acc += (u64)(j - i);
-        } else {
-          while (j < want) {
-            u8 cc = tile[j];
-            if (is_ws(cc)) break;
-            h ^= cc;
-            h *= FNV64_PRIME;
-            ++j;
-          }
-          if (j == want && base + j < n) {
-            long g = base + j;
-            while (g < n && !is_ws(text[g])) {
-              h ^= text[g];
-              h *= FNV64_PRIME;
-              ++g;
-            }
-            j = g - base;
-          }
-        }
-        if (mode == 3) {
-          acc += h;
-        } else if (mode >= 4) {
-          u64 k = remap_key(h);
-          u64 p = ((u64)(base + i) << 16) | (u64)(j - i);
-          u32 slot = (u32)((k ^ (k >> 32)) & (TOK_CACHE - 1));
-          bool done = false;
-          for (int pr = 0; pr < TOK_PROBE; ++pr) {
-            u64 cur = ckeys[slot];
-            if (cur == k) {
-              atomicAdd(&ccnt[slot], 1u);
-              done = true;
-              break;
-            }
-            if (cur == HT_EMPTY) {
-              u64 prevk = atomicCAS((unsigned long long*)&ckeys[slot],
-                                    (unsigned long long)HT_EMPTY,
-                                    (unsigned long long)k);
-              if (prevk == HT_EMPTY) cpos[slot] = p;
-              if (prevk == HT_EMPTY || prevk == k) {
-                atomicAdd(&ccnt[slot], 1u);
-                done = true;
-                break;
-              }
-            }
-            slot = (slot + 1) & (TOK_CACHE - 1);
-          }
-          if (!done) {
-            if (mode == 4) acc += k;
-            else {
-              sh[ns] = k;
-              sp[ns] = p;
-              ++ns;
-            }
-          }
-        }
-      }
-      prev = c;
-    }
-    if (mode >= 5 && ns) {
-      unsigned long long o = atomicAdd(spill_counter, (unsigned long long)ns);
-      for (int w = 0; w < ns; ++w)
-        if ((long)o + w < spill_cap) {
-          out_hash[o + w] = sh[w];
-          out_pos[o + w] = sp[w];
-        }
-    }
-  }
-  __syncthreads();
-  if (mode >= 4)
-    for (int s = threadIdx.x; s < TOK_CACHE; s += blockDim.x)
-      acc += ccnt[s];
-  if (acc) atomicAdd((unsigned long long*)sink, acc);
-}
-
 // ---------------------------------------------------------------------------
 // K5 bucketized count: input (hash, pos) grouped by top-8-bit bucket (one
 // radix partition pass).  grid = NBUCKETS x SLICES blocks; each block
@@ -1454,8 +857,8 @@ __global__ __launch_bounds__(256) void bucket_count_kernel(
     const u64* __restrict__ hashes, const u64* __restrict__ pos,
     const i64* __restrict__ bucket_off,  // [nbuckets+1] exclusive offsets,
                                          // OR per-bucket lengths when
-                                         // region_stride > 0 (bucketed
-                                         // direct spill: bucket b lives at
+                                         // region_stride > 0 (fixed-stride
+                                         // regions: bucket b lives at
                                          // [b*stride, b*stride+len[b]))
     int nbuckets, int slices, u64* __restrict__ tkeys,
     i64* __restrict__ tvals, u64* __restrict__ texm, u64 cap_mask,

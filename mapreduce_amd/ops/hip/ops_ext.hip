@@ -146,7 +146,7 @@ bool tok_v6_forced() {
   return f == 1;
 }
 
-static_assert(kBlock == V7_BLOCK, "v7 launches use kBlock threads");
+static_assert(kBlock == TOK_THREADS, "v6 / v7 launches use kBlock threads");
 
 // Which body the most recent v6/v7 tokenizer launch of this process
 // dispatched ("v7", "v6", or "none" before the first): set where the kernel
@@ -245,6 +245,66 @@ void check_dev_i64(const torch::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
 }
 
+unsigned long long* ullp(torch::Tensor& t) {
+  return reinterpret_cast<unsigned long long*>(t.data_ptr<i64>());
+}
+
+// GPOS side buffer: the block caches' exemplar positions live in global
+// memory instead of LDS (written once per distinct word per block).  One
+// persistent buffer per device, grown to the largest request; a kernel only
+// reads what it wrote itself, so launches share it.
+u64* tok_cpos_buffer(const torch::Device& dev, long entries) {
+  static std::map<int, torch::Tensor> bufs;
+  torch::Tensor& b = bufs[dev.index()];
+  if (!b.defined() || b.numel() < entries)
+    b = torch::empty({entries},
+                     torch::TensorOptions().device(dev).dtype(torch::kInt64));
+  return u64p(b);
+}
+
+// What a v6 / v7 launch takes besides its grid.
+struct TokArgs {
+  torch::Tensor text;
+  long pos_base;
+  u64* tkeys;  // global table (spill-all passes a dummy)
+  i64* tvals;
+  u64* texm;
+  u64 cap_mask;
+  u64* out_hash;  // spill stream
+  u64* out_pos;
+  unsigned long long* counter;
+  long spill_cap;
+  unsigned long long* nwords;
+  const i64* split_off = nullptr;  // COMPOSITE only
+  int nsplit_off = 0;
+  long doc_base = 0;
+};
+
+// The one place that picks the tokenizer body (tok_v6_forced) for a set of
+// template arguments and launches it.
+template <int CACHE_N, bool GPOS, bool SPILL_ALL = false,
+          bool COMPOSITE = false, int SCHUNK = 512>
+struct Tok {
+  static auto kernel() {
+    auto kfn = tokenize_v7_kernel<CACHE_N, GPOS, SPILL_ALL, COMPOSITE, SCHUNK>;
+    if (tok_v6_forced())
+      kfn = tokenize_v6_kernel<CACHE_N, GPOS, SPILL_ALL, COMPOSITE, SCHUNK>;
+    return kfn;
+  }
+
+  static void launch(long blocks, TokArgs a) {
+    g_tok_last_body = tok_v6_forced() ? "v6" : "v7";
+    u64* cpos =
+        GPOS ? tok_cpos_buffer(a.text.device(), blocks * CACHE_N) : nullptr;
+    auto kfn = kernel();
+    hipLaunchKernelGGL(kfn, dim3(blocks), dim3(kBlock), 0, cur_stream(),
+                       a.text.data_ptr<u8>(), (long)a.text.numel(),
+                       (u64)a.pos_base, a.tkeys, a.tvals, a.texm, a.cap_mask,
+                       a.out_hash, a.out_pos, a.counter, a.spill_cap,
+                       a.nwords, cpos, a.split_off, a.nsplit_off, a.doc_base);
+  }
+};
+
 }  // namespace
 
 // ---------------------------------------------------------------------- K2/K3
@@ -282,11 +342,10 @@ void tokenize_count(torch::Tensor text, long pos_base, torch::Tensor tkeys,
                      reinterpret_cast<unsigned long long*>(nwords.data_ptr<i64>()));
 }
 
-// ---------------------------------------------------- K2 streaming (v2)
+// ------------------------------------------------------ K2 streaming (v2)
 // every word spilled via the wave-chunked allocator (no cache) — chunk
 // tails are HT_EMPTY-padded, so consumers must filter/skip them.  The
-// inverted-index tokenize path; replaces tokenize_spill's per-window
-// shared-counter atomics (cross-XCD contention, see tokenize_v6 note).
+// inverted-index tokenize path.
 std::vector<torch::Tensor> tokenize_spill_v2(torch::Tensor text,
                                              long pos_base, long cap,
                                              long max_blocks) {
@@ -308,19 +367,10 @@ std::vector<torch::Tensor> tokenize_spill_v2(torch::Tensor text,
     // cache to warm or flush, and the inverted index measured 8.05-8.08
     // ms/job on the one-round grid vs 8.03-8.06 on this one (parent
     // 8.02-8.07; profiles/tokenizer_occupancy_r04.md)
-    auto kfn = tokenize_v7_kernel<16, false, true>;
-    if (tok_v6_forced()) kfn = tokenize_v6_kernel<16, false, 4096, 0, true>;
-    g_tok_last_body = tok_v6_forced() ? "v6" : "v7";
-    hipLaunchKernelGGL(kfn,
-                       dim3(tok_cap_blocks(grid_for(n, TOK_BYTES), max_blocks)),
-                       dim3(kBlock), 0,
-                       cur_stream(), text.data_ptr<u8>(), n, (u64)pos_base,
-                       u64p(dummy), dummy.data_ptr<i64>(), nullptr,
-                       (u64)15, u64p(out_hash), u64p(out_pos),
-                       reinterpret_cast<unsigned long long*>(counter.data_ptr<i64>()),
-                       cap,
-                       reinterpret_cast<unsigned long long*>(nwords.data_ptr<i64>()),
-                       nullptr, (const i64*)nullptr, 0, 0L);
+    Tok<16, false, true>::launch(
+        tok_cap_blocks(grid_for(n, TOK_BYTES), max_blocks),
+        {text, pos_base, u64p(dummy), dummy.data_ptr<i64>(), nullptr, (u64)15,
+         u64p(out_hash), u64p(out_pos), ullp(counter), cap, ullp(nwords)});
   }
   return {out_hash, out_pos, counter, nwords};
 }
@@ -339,21 +389,11 @@ std::vector<torch::Tensor> tokenize_spill_composite(
   auto nwords = torch::zeros({1}, opts);
   if (n) {
     auto dummy = torch::empty({16}, opts);
-    auto kfn = tokenize_v7_kernel<16, false, true, true>;
-    if (tok_v6_forced())
-      kfn = tokenize_v6_kernel<16, false, 4096, 0, true, true>;
-    g_tok_last_body = tok_v6_forced() ? "v6" : "v7";
-    hipLaunchKernelGGL(kfn,
-                       dim3(tok_cap_blocks(grid_for(n, TOK_BYTES), max_blocks)),
-                       dim3(kBlock), 0,
-                       cur_stream(), text.data_ptr<u8>(), n, (u64)pos_base,
-                       u64p(dummy), dummy.data_ptr<i64>(), nullptr,
-                       (u64)15, u64p(out_hash), u64p(out_pos),
-                       reinterpret_cast<unsigned long long*>(counter.data_ptr<i64>()),
-                       cap,
-                       reinterpret_cast<unsigned long long*>(nwords.data_ptr<i64>()),
-                       nullptr, split_off.data_ptr<i64>(),
-                       (int)split_off.numel(), doc_base);
+    Tok<16, false, true, true>::launch(
+        tok_cap_blocks(grid_for(n, TOK_BYTES), max_blocks),
+        {text, pos_base, u64p(dummy), dummy.data_ptr<i64>(), nullptr, (u64)15,
+         u64p(out_hash), u64p(out_pos), ullp(counter), cap, ullp(nwords),
+         split_off.data_ptr<i64>(), (int)split_off.numel(), doc_base});
   }
   return {out_hash, out_pos, counter, nwords};
 }
@@ -379,52 +419,30 @@ void tokenize_cache_spill_composite(
   TORCH_CHECK(out_hash.numel() >= spill_cap && out_pos.numel() >= spill_cap,
               "spill arrays too small");
   if (!n) return;
-  auto kfn = tokenize_v7_kernel<2048, true, false, true, 2048>;
-  if (tok_v6_forced())
-    kfn = tokenize_v6_kernel<2048, true, 4096, 0, false, true, 2048, 0, 256>;
-  g_tok_last_body = tok_v6_forced() ? "v6" : "v7";
-  long blocks = tok_cap_blocks(tok_grid(kfn, kBlock, n, 4096), max_blocks);
-  static torch::Tensor cpos_gc;  // persistent GPOS side-buffer
-  long need = blocks * 2048;
-  if (!cpos_gc.defined() || cpos_gc.numel() < need ||
-      cpos_gc.device() != text.device())
-    cpos_gc = torch::empty({need}, torch::TensorOptions()
-                                        .device(text.device())
-                                        .dtype(torch::kInt64));
-  hipLaunchKernelGGL(
-      kfn, dim3(blocks), dim3(kBlock), 0, cur_stream(), text.data_ptr<u8>(), n,
-      (u64)pos_base, u64p(tkeys), tvals.data_ptr<i64>(),
-      texm.numel() ? u64p(texm) : nullptr, (u64)(cap - 1), u64p(out_hash),
-      u64p(out_pos),
-      reinterpret_cast<unsigned long long*>(counter.data_ptr<i64>()),
-      spill_cap,
-      reinterpret_cast<unsigned long long*>(nwords.data_ptr<i64>()),
-      u64p(cpos_gc), split_off.data_ptr<i64>(), (int)split_off.numel(),
-      doc_base);
+  using T = Tok<2048, true, false, true, 2048>;
+  T::launch(
+      tok_cap_blocks(tok_grid(T::kernel(), kBlock, n, 4096), max_blocks),
+      {text, pos_base, u64p(tkeys), tvals.data_ptr<i64>(),
+       texm.numel() ? u64p(texm) : nullptr, (u64)(cap - 1), u64p(out_hash),
+       u64p(out_pos), ullp(counter), spill_cap, ullp(nwords),
+       split_off.data_ptr<i64>(), (int)split_off.numel(), doc_base});
 }
 
-// ------------------------------------------------------------- K2 streaming
-std::vector<torch::Tensor> tokenize_spill(torch::Tensor text, long pos_base,
-                                          long cap) {
-  TORCH_CHECK(text.is_cuda() && text.scalar_type() == torch::kUInt8 &&
-              text.is_contiguous(), "text must be contiguous u8 on GPU");
-  long n = text.numel();
-  auto opts = torch::TensorOptions().device(text.device()).dtype(torch::kInt64);
-  auto out_hash = torch::empty({cap}, opts);
-  auto out_pos = torch::empty({cap}, opts);
-  auto counter = torch::zeros({1}, opts);
-  if (n)
-    hipLaunchKernelGGL(tokenize_spill_kernel, dim3(grid_for(n, TOK_BYTES)),
-                       dim3(kBlock), 0, cur_stream(), text.data_ptr<u8>(), n,
-                       (u64)pos_base, u64p(out_hash), u64p(out_pos),
-                       reinterpret_cast<unsigned long long*>(counter.data_ptr<i64>()),
-                       cap);
-  return {out_hash, out_pos, counter};
-}
-
-// -------------------------------------------------------------- K2+K5 v4
-// out arrays + counter are caller-owned so several map-job launches can
-// append into ONE spill stream (atomic counter composes across launches)
+// ---------------------------------------------------------------- K2+K5
+// Word count: the LDS cache counts the Zipf head, misses spill.  The out
+// arrays + counter are caller-owned so several map-job launches can append
+// into ONE spill stream (atomic counter composes across launches).
+//
+// The shape is fixed at what the sweeps chose (ms/step on the bench shape):
+// 2048 cache slots per block (512 = 5.52, 1024 = 5.26, 2048 = 4.94 — fewer
+// spills beat occupancy here) and, with GPOS, 2048-entry spill chunks:
+// reservation-stall amortization vs HT_EMPTY pad waste measured 128 = 3.86,
+// 512 = 1.93, 1024 = 1.92, 2048 = 1.84, 4096 = 3.09 over ~15M real misses
+// and 8192 waves — one grab per wave is the sweet spot; 4096 doubles the
+// reserved entries (19M pads flood the radix+bucket pipeline at ~75 ns
+// each).  An 8 KB tile and 512-thread blocks measured slower.
+// MR_TOK_GPOS=0 keeps the exemplar positions in LDS (default on: 4.90 vs
+// 5.05 ms); that shape keeps its 512-entry chunks.
 void tokenize_cache_spill(
     torch::Tensor text, long pos_base, torch::Tensor tkeys,
     torch::Tensor tvals, torch::Tensor texm, long spill_cap,
@@ -437,251 +455,22 @@ void tokenize_cache_spill(
   TORCH_CHECK((cap & (cap - 1)) == 0, "table capacity must be a power of 2");
   TORCH_CHECK(out_hash.numel() >= spill_cap && out_pos.numel() >= spill_cap,
               "spill arrays too small");
-  if (n) {
-    // Default v7 (v6 with the next tile prefetched into registers and a
-    // cheaper first-chunk extract; MR_TOKENIZE_V6=1 for v6).  v6: branchless
-    // ws-mask scan + register-funnel hashing in v4's single-phase structure
-    // — measured 5.10 vs 6.25 ms/step (+23%) over v4's per-byte scan.
-    // Recorded alternatives: MR_TOKENIZE_V4=1
-    // (per-byte scan loop), MR_TOKENIZE_V5=1 (word-list restructure,
-    // measured 2x SLOWER: extra barriers + LDS footprint outweigh lane
-    // balance at this grain).
-    const char* v = getenv("MR_TOKENIZE_V5");
-    const char* v4 = getenv("MR_TOKENIZE_V4");
-    if (!(v && v[0] == '1') && !(v4 && v4[0] == '1')) {
-      // MR_TOK_CACHE ∈ {512, 1024, 2048}: LDS-cache slots per block —
-      // occupancy (smaller cache -> more blocks/CU) vs spill volume
-      const char* cs = getenv("MR_TOK_CACHE");
-      int cache = cs ? atoi(cs) : 2048;  // sweep: 512=5.52, 1024=5.26,
-                                         // 2048=4.94 ms/step — fewer
-                                         // spills beat occupancy here
-      const char* gp = getenv("MR_TOK_GPOS");
-      bool gpos = !(gp && gp[0] == '0');  // default ON: 4.90 vs 5.05 ms
-      const char* ts = getenv("MR_TOK_TILE");
-      int tsz = ts ? atoi(ts) : 4096;
-      // MR_SPILL_CHUNK ∈ {128, 512, 1024, 2048, 4096}: reservation-stall
-      // amortization vs HT_EMPTY pad waste.  Measured (Europarl shape,
-      // ~15M real misses over 8192 waves): 128=3.86, 512=1.93, 1024=1.92,
-      // 2048=1.84, 4096=3.09 ms/step — one grab per wave (2048) is the
-      // sweet spot; 4096 doubles reserved entries (19M pads flood the
-      // radix+bucket pipeline at ~75 ns each)
-      const char* sc = getenv("MR_SPILL_CHUNK");
-      int schunk = sc ? atoi(sc) : 2048;
-      // MR_TOK_BLOCK=512: 8 KB tile in ONE window pass (same per-thread
-      // geometry as 256/4096) — +2 KB LDS for 2x waves/block, occupancy
-      // probe from when the tokenizer was read as wait-bound (its VALU
-      // is ~74 % busy across the 4 waves of a SIMD: round 7)
-      const char* tb = getenv("MR_TOK_BLOCK");
-      int blockn = (tb && atoi(tb) == 512) ? 512 : 256;
-      if (blockn == 512) tsz = 8192;
-      auto kfn = tokenize_v6_kernel<2048, false, 4096>;
-      if (gpos && blockn == 512)
-        kfn = tokenize_v6_kernel<2048, true, 8192, 0, false, false, 2048,
-                                 0, 512>;
-      else if (gpos && tsz == 8192) kfn = tokenize_v6_kernel<2048, true, 8192>;
-      else if (gpos && cache == 4096) kfn = tokenize_v6_kernel<4096, true, 4096>;
-      else if (gpos && cache == 1024) kfn = tokenize_v6_kernel<1024, true, 4096>;
-      else if (gpos && schunk == 128)
-        kfn = tokenize_v6_kernel<2048, true, 4096, 0, false, false, 128>;
-      else if (gpos && schunk == 1024)
-        kfn = tokenize_v6_kernel<2048, true, 4096, 0, false, false, 1024>;
-      else if (gpos && schunk == 2048)
-        kfn = tokenize_v6_kernel<2048, true, 4096, 0, false, false, 2048>;
-      else if (gpos && schunk == 4096)
-        kfn = tokenize_v6_kernel<2048, true, 4096, 0, false, false, 4096>;
-      else if (gpos) kfn = tokenize_v6_kernel<2048, true, 4096>;
-      else if (cache == 512) kfn = tokenize_v6_kernel<512, false, 4096>;
-      else if (cache == 1024) kfn = tokenize_v6_kernel<1024, false, 4096>;
-      else if (schunk == 128)
-        kfn = tokenize_v6_kernel<2048, false, 4096, 0, false, false, 128>;
-      // the two shapes the job runs (every knob at its default, GPOS on
-      // or off) take the v7 body; the sweep shapes above stay v6 bodies
-      g_tok_last_body = "v6";
-      if (!tok_v6_forced() && cache == 2048 && tsz == 4096 &&
-          schunk == 2048 && blockn == V7_BLOCK) {
-        if (gpos) kfn = tokenize_v7_kernel<2048, true, false, false, 2048>;
-        else kfn = tokenize_v7_kernel<2048, false>;
-        g_tok_last_body = "v7";
-      }
-      long blocks = tok_cap_blocks(tok_grid(kfn, blockn, n, tsz), max_blocks);
-      static torch::Tensor cpos_g;  // persistent side-buffer (GPOS only)
-      u64* cpg = nullptr;
-      if (gpos) {
-        long need = blocks * (cache > 2048 ? cache : 2048);
-        if (!cpos_g.defined() || cpos_g.numel() < need ||
-            cpos_g.device() != text.device())
-          cpos_g = torch::empty({need},
-                                torch::TensorOptions().device(text.device())
-                                    .dtype(torch::kInt64));
-        cpg = u64p(cpos_g);
-      }
-      hipLaunchKernelGGL(kfn,
-                         dim3(blocks), dim3(blockn), 0,
-                         cur_stream(), text.data_ptr<u8>(), n, (u64)pos_base,
-                         u64p(tkeys), tvals.data_ptr<i64>(),
-                         texm.numel() ? u64p(texm) : nullptr, (u64)(cap - 1),
-                         u64p(out_hash), u64p(out_pos),
-                         reinterpret_cast<unsigned long long*>(counter.data_ptr<i64>()),
-                         spill_cap,
-                         reinterpret_cast<unsigned long long*>(nwords.data_ptr<i64>()),
-                         cpg, (const i64*)nullptr, 0, 0L);
-    } else if (!(v && v[0] == '1'))
-      hipLaunchKernelGGL(tokenize_cache_spill_kernel,
-                         dim3(grid_for(n, TOK_BYTES)), dim3(kBlock), 0,
-                         cur_stream(), text.data_ptr<u8>(), n, (u64)pos_base,
-                         u64p(tkeys), tvals.data_ptr<i64>(),
-                         texm.numel() ? u64p(texm) : nullptr, (u64)(cap - 1),
-                         u64p(out_hash), u64p(out_pos),
-                         reinterpret_cast<unsigned long long*>(counter.data_ptr<i64>()),
-                         spill_cap,
-                         reinterpret_cast<unsigned long long*>(nwords.data_ptr<i64>()));
-    else  // MR_TOKENIZE_V5=1
-      hipLaunchKernelGGL(tokenize_v5_kernel,
-                         dim3(grid_for(n, TOK_BYTES)), dim3(kBlock), 0,
-                         cur_stream(), text.data_ptr<u8>(), n, (u64)pos_base,
-                         u64p(tkeys), tvals.data_ptr<i64>(),
-                         texm.numel() ? u64p(texm) : nullptr, (u64)(cap - 1),
-                         u64p(out_hash), u64p(out_pos),
-                         reinterpret_cast<unsigned long long*>(counter.data_ptr<i64>()),
-                         spill_cap,
-                         reinterpret_cast<unsigned long long*>(nwords.data_ptr<i64>()));
-  }
-}
-
-// ----------------------------------------------------- K2+K5 bucketed spill
-// v6 with NBKT=256: misses land directly in per-top-byte-bucket regions of
-// the (caller-owned) spill arrays — no radix_pass(56) bucketize afterwards.
-// counters: i64[256] per-bucket lengths (zeroed by the caller per job);
-// spill_bcap: per-bucket region capacity (out arrays hold 256*spill_bcap).
-// Overflowing buckets run their counter past spill_bcap with writes dropped
-// — the host detects via counters.max() > spill_bcap and fails loudly.
-void tokenize_cache_spill_bucketed(
-    torch::Tensor text, long pos_base, torch::Tensor tkeys,
-    torch::Tensor tvals, torch::Tensor texm, long spill_bcap,
-    torch::Tensor nwords, torch::Tensor out_hash, torch::Tensor out_pos,
-    torch::Tensor counters) {
-  TORCH_CHECK(text.is_cuda() && text.scalar_type() == torch::kUInt8 &&
-              text.is_contiguous(), "text must be contiguous u8 on GPU");
-  long n = text.numel();
-  long cap = tkeys.numel();
-  TORCH_CHECK((cap & (cap - 1)) == 0, "table capacity must be a power of 2");
-  TORCH_CHECK(counters.numel() >= 256, "counters must hold 256 buckets");
-  TORCH_CHECK(out_hash.numel() >= 256 * spill_bcap &&
-              out_pos.numel() >= 256 * spill_bcap, "spill arrays too small");
   if (!n) return;
   const char* gp = getenv("MR_TOK_GPOS");
   bool gpos = !(gp && gp[0] == '0');
-  auto kfn = tokenize_v6_kernel<2048, false, 4096, 0, false, false, 512, 256>;
-  if (gpos)
-    kfn = tokenize_v6_kernel<2048, true, 4096, 0, false, false, 512, 256>;
-  long blocks = tok_grid(kfn, kBlock, n, 4096);
-  static torch::Tensor cpos_gb;  // persistent GPOS side-buffer
-  u64* cpg = nullptr;
+  TokArgs a{text, pos_base, u64p(tkeys), tvals.data_ptr<i64>(),
+            texm.numel() ? u64p(texm) : nullptr, (u64)(cap - 1),
+            u64p(out_hash), u64p(out_pos), ullp(counter), spill_cap,
+            ullp(nwords)};
   if (gpos) {
-    long need = blocks * 2048;
-    if (!cpos_gb.defined() || cpos_gb.numel() < need ||
-        cpos_gb.device() != text.device())
-      cpos_gb = torch::empty({need},
-                             torch::TensorOptions().device(text.device())
-                                 .dtype(torch::kInt64));
-    cpg = u64p(cpos_gb);
+    using T = Tok<2048, true, false, false, 2048>;
+    T::launch(
+        tok_cap_blocks(tok_grid(T::kernel(), kBlock, n, 4096), max_blocks), a);
+  } else {
+    using T = Tok<2048, false>;
+    T::launch(
+        tok_cap_blocks(tok_grid(T::kernel(), kBlock, n, 4096), max_blocks), a);
   }
-  hipLaunchKernelGGL(kfn, dim3(blocks), dim3(kBlock), 0, cur_stream(),
-                     text.data_ptr<u8>(), n, (u64)pos_base, u64p(tkeys),
-                     tvals.data_ptr<i64>(),
-                     texm.numel() ? u64p(texm) : nullptr, (u64)(cap - 1),
-                     u64p(out_hash), u64p(out_pos),
-                     reinterpret_cast<unsigned long long*>(counters.data_ptr<i64>()),
-                     spill_bcap,
-                     reinterpret_cast<unsigned long long*>(nwords.data_ptr<i64>()),
-                     cpg, (const i64*)nullptr, 0, 0L);
-}
-
-// v6-structure ablation: mode 1=stage+classify, 2=+hash, 3=+cache, 0=full
-double tok6_ablate(torch::Tensor text, long mode, long iters) {
-  long n = text.numel();
-  auto opts = torch::TensorOptions().device(text.device()).dtype(torch::kInt64);
-  long tcap = 1 << 19;
-  auto tkeys = torch::full({tcap}, -1, opts);
-  auto tvals = torch::zeros({tcap}, opts);
-  auto texm = torch::zeros({tcap}, opts);
-  long cap = n / 2 + 16;
-  auto oh = torch::empty({cap}, opts);
-  auto op = torch::empty({cap}, opts);
-  auto ctr = torch::zeros({1}, opts);
-  auto nw = torch::zeros({1}, opts);
-  auto kfn = tokenize_v6_kernel<2048, true, 4096, 0>;
-  if (mode == 1) kfn = tokenize_v6_kernel<2048, true, 4096, 1>;
-  else if (mode == 2) kfn = tokenize_v6_kernel<2048, true, 4096, 2>;
-  else if (mode == 3) kfn = tokenize_v6_kernel<2048, true, 4096, 3>;
-  else if (mode == 4) kfn = tokenize_v6_kernel<2048, true, 4096, 4>;
-  long blocks = tok_grid(kfn, kBlock, n, 4096);
-  auto cpg = torch::empty({blocks * 2048}, opts);
-  hipStream_t st = cur_stream();
-  hipEvent_t e0, e1;
-  hipEventCreate(&e0);
-  hipEventCreate(&e1);
-  auto launch = [&]() {
-    hipLaunchKernelGGL(kfn, dim3(blocks), dim3(kBlock), 0, st,
-                       text.data_ptr<u8>(), n, (u64)0, u64p(tkeys),
-                       tvals.data_ptr<i64>(), u64p(texm), (u64)(tcap - 1),
-                       u64p(oh), u64p(op),
-                       reinterpret_cast<unsigned long long*>(ctr.data_ptr<i64>()),
-                       cap,
-                       reinterpret_cast<unsigned long long*>(nw.data_ptr<i64>()),
-                       u64p(cpg), (const i64*)nullptr, 0, 0L);
-  };
-  launch();  // warm
-  hipEventRecord(e0, st);
-  for (long i = 0; i < iters; ++i) {
-    ctr.zero_();
-    launch();
-  }
-  hipEventRecord(e1, st);
-  hipEventSynchronize(e1);
-  float ms = 0;
-  hipEventElapsedTime(&ms, e0, e1);
-  hipEventDestroy(e0);
-  hipEventDestroy(e1);
-  return (double)ms / iters;
-}
-
-// diagnosis only
-double tok_ablate(torch::Tensor text, long mode, long iters) {
-  long n = text.numel();
-  auto opts = torch::TensorOptions().device(text.device()).dtype(torch::kInt64);
-  auto sink = torch::zeros({1}, opts);
-  long cap = n / 2 + 16;
-  auto oh = torch::empty({mode >= 5 ? cap : 1}, opts);
-  auto op = torch::empty({mode >= 5 ? cap : 1}, opts);
-  auto ctr = torch::zeros({1}, opts);
-  hipStream_t st = cur_stream();
-  hipEvent_t e0, e1;
-  hipEventCreate(&e0);
-  hipEventCreate(&e1);
-  // warm
-  hipLaunchKernelGGL(tok_ablate_kernel, dim3(grid_for(n, TOK_BYTES)),
-                     dim3(kBlock), 0, st, text.data_ptr<u8>(), n, (int)mode,
-                     nullptr, sink.data_ptr<i64>(), u64p(oh), u64p(op),
-                     reinterpret_cast<unsigned long long*>(ctr.data_ptr<i64>()),
-                     cap);
-  hipEventRecord(e0, st);
-  for (long i = 0; i < iters; ++i) {
-    ctr.zero_();
-    hipLaunchKernelGGL(tok_ablate_kernel, dim3(grid_for(n, TOK_BYTES)),
-                       dim3(kBlock), 0, st, text.data_ptr<u8>(), n,
-                       (int)mode, nullptr, sink.data_ptr<i64>(), u64p(oh),
-                       u64p(op),
-                       reinterpret_cast<unsigned long long*>(ctr.data_ptr<i64>()),
-                       cap);
-  }
-  hipEventRecord(e1, st);
-  hipEventSynchronize(e1);
-  float ms = 0;
-  hipEventElapsedTime(&ms, e0, e1);
-  hipEventDestroy(e0);
-  hipEventDestroy(e1);
-  return (double)ms / iters;
 }
 
 // ---------------------------------------------------------- K5 bucket count
@@ -706,7 +495,7 @@ void bucket_count(torch::Tensor hashes, torch::Tensor pos,
                   (texm.numel() == 0 || texm.numel() == cap),
               "tvals (and texm, when tracked) must match tkeys");
   // region_stride > 0: bucket_off holds per-bucket LENGTHS and bucket b's
-  // data lives at [b*stride, b*stride+len[b]) (bucketed direct spill)
+  // data lives at [b*stride, b*stride+len[b]) (fixed-stride regions)
   TORCH_CHECK(bucket_off.numel() >= (region_stride > 0 ? nbuckets
                                                        : nbuckets + 1),
               "bucket_off size");
@@ -2093,9 +1882,7 @@ std::vector<torch::Tensor> pagerank_update(torch::Tensor sums,
 // register count and static LDS are what decide it), and which body this
 // process runs ("v7", or "v6" under MR_TOKENIZE_V6=1).
 py::dict tokenizer_occupancy() {
-  auto kfn = tokenize_v7_kernel<2048, true, false, false, 2048>;
-  if (tok_v6_forced())
-    kfn = tokenize_v6_kernel<2048, true, 4096, 0, false, false, 2048>;
+  auto kfn = Tok<2048, true, false, false, 2048>::kernel();
   TokOccupancy o = tok_occupancy(reinterpret_cast<const void*>(kfn), kBlock);
   hipFuncAttributes fa;
   C10_HIP_CHECK(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kfn)));
@@ -2209,18 +1996,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("tokenize_spill_v2", &tokenize_spill_v2, py::arg("text"),
         py::arg("pos_base"), py::arg("cap"), py::arg("max_blocks") = 0,
         "spill-all tokenizer (chunk-padded; filter HT_EMPTY)");
-  m.def("tokenize_spill", &tokenize_spill,
-        "tokenize -> compact (hash,pos) arrays");
-  m.def("tokenize_cache_spill", &tokenize_cache_spill, py::arg("text"),
+  m.def("tokenize_cache_spill",&tokenize_cache_spill, py::arg("text"),
         py::arg("pos_base"), py::arg("tkeys"), py::arg("tvals"),
         py::arg("texm"), py::arg("spill_cap"), py::arg("nwords"),
         py::arg("out_hash"), py::arg("out_pos"), py::arg("counter"),
         py::arg("max_blocks") = 0,
         "tokenize; LDS cache counts the head, misses spill");
-  m.def("tokenize_cache_spill_bucketed", &tokenize_cache_spill_bucketed,
-        "tokenize; misses spill directly into per-top-byte-bucket regions");
-  m.def("tok_ablate", &tok_ablate, "ablation timing (diagnosis)");
-  m.def("tok6_ablate", &tok6_ablate, "v6 ablation timing");
   m.def("bucket_count", &bucket_count,
         "LDS count of bucket-partitioned (hash,pos)");
   m.def("hash_insert_count", &hash_insert_count);

@@ -91,11 +91,6 @@ def test_build_from_files_and_query(tmp_path):
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(
-    __import__("os").environ.get("MR_TOKENIZE_V4") == "1"
-    or __import__("os").environ.get("MR_TOKENIZE_V5") == "1",
-    reason="serving lookups need the v6 wordhash64 keys (archived "
-           "tokenizers predate the migration)")
 def test_serve_gpu_results(tmp_path):
     """Results built on the GPU tier stay device-resident while served."""
     from mapreduce_amd.serve import build_results_from_files
